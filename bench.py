@@ -10,16 +10,24 @@ computes stays inside the timed region: every lie (a faulty general's coin
 flip, ba.py:45, 269) is drawn from Philox in the kernel, every tree level and
 majority is resolved, every lieutenant's root decision is written to HBM
 (uint64/trial), plus the per-trial quorum/IC outcome byte and run counters.
-`value_with_input_generation` repeats the timing with the inputs drawn inside
-the kernel too.  Both passes follow a common warm-up of >= 1 s of back-to-back
-steps, so neither pays the clock ramp.
+The timed pass follows a warm-up of >= 1 s of back-to-back steps, so it does not
+pay the clock ramp.
+
+A plain run does only what `value` needs: stage the inputs, warm up, time the
+--steps steps, print the line.  --dump-outputs DIR also writes what the last
+timed step produced (dump_outputs below), so two builds can be compared output
+for output: the same arguments give the same inputs on every run.  --full adds
+every side measurement, each a pass of its own after the timed one:
+`value_with_input_generation` (the inputs drawn inside the kernel too),
+`value_single_stream`, the clock pass, the per-kernel profiling pass with the
+rooflines, and the CPU baseline with its counter check.
 
 Steps in flight (--streams, default 2): step i is enqueued on stream i % 2, each
 stream with its own library ctx and output buffers, so two steps can run at
 once.  A WAVE launch's last ~quarter runs one wave per SIMD (the SIMD's older
 wave wins issue arbitration and finishes first); the next step's waves fill
-those slots.  Every step is still a complete 1M-trial pass; the counters of
-all K steps are checked against a one-stream pass of the same steps, reported
+those slots.  Every step is still a complete 1M-trial pass; with --full the counters
+of all K steps are checked against a one-stream pass of the same steps, reported
 as `value_single_stream`, whose per-step HIP-event time is also the kernel's
 launch time the roofline uses (and that rocprofv3 reports for --streams 1).
 
@@ -33,7 +41,8 @@ leave it together.  torch.distributed (gloo) carries the RCCL unique id and
 the max-over-ranks of the wall time.  (A gloo barrier inside the timed region
 would add a host TCP round trip to a ~1 ms region.)
 
-Prints ONE JSON line (rank 0).  DESIGN.md §5 gives the roofline accounting:
+Prints ONE JSON line (rank 0).  With --full it carries the rooflines, whose
+accounting DESIGN.md §5 gives:
 `roofline` is the dominant kernel's HBM roofline on the bytes it must move
 (its per-trial inputs and outputs), `valu_roofline` its vector-issue roofline
 from the committed rocprofv3 counters of the same build, `compute_roofline`
@@ -266,6 +275,46 @@ def clock_from_probes(p0, p1):
     return (statistics.median(mhz.values()) if mhz else None), mhz
 
 
+DUMP_MAX_BYTES = 64 * 10**6  # --dump-outputs: all files of one rank together
+DUMP_TRIAL_BYTES = 8 + 8 + 4 + 8  # decisions_lo, decisions_hi, outcome, trial_index
+DUMP_SAMPLE_SEED = 0xD0
+
+
+def dump_outputs(dirname, decisions, outcome, counters, first, suffix=""):
+    """--dump-outputs: what a caller of the timed path holds after the last timed
+    step, as DIR/<name><suffix>.npy (suffix: `_rank<r>` at world > 1):
+
+      decisions_lo, decisions_hi  float64 [T]  the low and high 32 bits of each trial's
+                                               uint64 decision word (exact in float64)
+      outcome                     float32 [T]  the per-trial quorum / IC outcome byte
+      counters                    float64 [16] the run counters summed over the timed steps
+      trial_index                 float64 [T]  global index of each trial written
+
+    T is the step's batch, or, where that would pass DUMP_MAX_BYTES, a fixed seeded
+    sample of it in ascending order (the same trials on every run and every build).
+    `decisions` / `outcome` are the last step's host arrays (uint64 / uint8),
+    `first` its first global trial index.  Returns the list of files written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    batch = int(decisions.shape[0])
+    keep = (DUMP_MAX_BYTES - (1 << 16)) // DUMP_TRIAL_BYTES  # 64 KiB for headers and counters
+    idx = np.arange(batch, dtype=np.int64)
+    if batch > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(batch, keep, replace=False))
+    d = np.ascontiguousarray(decisions).view(np.uint64)[idx]
+    arrays = {"decisions_lo": (d & np.uint64(0xFFFFFFFF)).astype(np.float64),
+              "decisions_hi": (d >> np.uint64(32)).astype(np.float64),
+              "outcome": np.asarray(outcome)[idx].astype(np.float32),
+              "counters": np.asarray(counters, dtype=np.float64),
+              "trial_index": (idx + first).astype(np.float64)}
+    files = []
+    for name, a in arrays.items():
+        path = os.path.join(dirname, f"{name}{suffix}.npy")
+        np.save(path, a)
+        files.append(os.path.basename(path))
+    return files
+
+
 def first_trial(i: int, rank: int, world: int, batch: int) -> int:
     """Global index of the first trial of step slot i on `rank`: slot i of the
     job is world x batch consecutive trials, rank r's shard the r-th batch of
@@ -332,9 +381,16 @@ def main():
     ap.add_argument("--engine", default="auto", choices=["auto", "fused", "levels"])
     ap.add_argument("--warm-s", type=float, default=1.0,
                     help="common warm-up: back-to-back steps before any timed pass")
-    ap.add_argument("--cpu-budget-s", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed pass, also run every side measurement: in-kernel input "
+                         "generation, one stream, the clock pass, the per-kernel profiling pass with "
+                         "the rooflines, and the CPU baseline with its counter check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's decisions and outcomes and the timed steps' "
+                         "counters as DIR/<name>.npy (float32/float64, at most 64 MB)")
+    ap.add_argument("--cpu-budget-s", type=float, default=12.0, help="with --full")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the profiling pass")
     ap.add_argument("--inputs-in-kernel", action="store_true",
                     help="draw faulty sets/orders inside the timed kernel (no staging)")
     ap.add_argument("--streams", type=int, default=2,
@@ -518,31 +574,42 @@ def main():
     counters = dict(zip(L.COUNTER_NAMES, [int(x) for x in cnt.cpu().tolist()]))
     local_counters = dict(zip(L.COUNTER_NAMES, [int(x) for x in local_cnt.cpu().tolist()]))
     value = total_trials / T
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's own buffers (step i ran on ctx i % NS), read before any
+        # later pass reuses them, and this rank's counters over the timed steps
+        last = base + args.steps - 1
+        dumped = dump_outputs(args.dump_outputs, decs[last % NS].cpu().numpy(),
+                              outs[last % NS].cpu().numpy(), local_cnt.cpu().numpy(),
+                              first_of(last), f"_rank{rank}" if world > 1 else "")
     value_gen = gen_ms = None
-    if not args.inputs_in_kernel:
+    if args.full and not args.inputs_in_kernel:
         T2, gen_ms = timed(base, True)  # same trials, inputs drawn in the kernel
         counters2 = dict(zip(L.COUNTER_NAMES, [int(x) for x in cnt.cpu().tolist()]))
         if counters2 != counters:
             raise SystemExit(f"staged-input and in-kernel-input runs disagree: {counters} vs {counters2}")
         value_gen = total_trials / T2
-    # the same steps one at a time on one stream: the single-stream rate, and (one launch
-    # per step) the kernel's own average launch time for the roofline below
-    T1, gpu_ms_1 = timed(base, args.inputs_in_kernel, 1)
-    counters1 = dict(zip(L.COUNTER_NAMES, [int(x) for x in cnt.cpu().tolist()]))
-    if counters1 != counters:
-        raise SystemExit(f"{NS}-stream and one-stream runs disagree: {counters} vs {counters1}")
-    value_1 = total_trials / T1
-    # the clock pass: the timed region's steps again (untimed), bracketed by two
-    # engine-clock probes on the launch stream (attributes a run's
-    # rate to the clock it ran at)
-    Tc, gpu_ms_c = timed(base, args.inputs_in_kernel, NS, probe=True)
-    pr = probes.cpu().numpy()
-    sclk, sclk_xcd = clock_from_probes(pr[0], pr[1])
+    value_1 = gpu_ms_1 = gpu_ms_c = sclk = None
+    sclk_xcd = {}
+    if args.full:
+        # the same steps one at a time on one stream: the single-stream rate, and (one launch
+        # per step) the kernel's own average launch time for the roofline below
+        T1, gpu_ms_1 = timed(base, args.inputs_in_kernel, 1)
+        counters1 = dict(zip(L.COUNTER_NAMES, [int(x) for x in cnt.cpu().tolist()]))
+        if counters1 != counters:
+            raise SystemExit(f"{NS}-stream and one-stream runs disagree: {counters} vs {counters1}")
+        value_1 = total_trials / T1
+        # the clock pass: the timed region's steps again (untimed), bracketed by two
+        # engine-clock probes on the launch stream (attributes a run's
+        # rate to the clock it ran at)
+        Tc, gpu_ms_c = timed(base, args.inputs_in_kernel, NS, probe=True)
+        pr = probes.cpu().numpy()
+        sclk, sclk_xcd = clock_from_probes(pr[0], pr[1])
 
     # per-kernel HIP-event timing on the launch stream (a further pass of new steps)
     kernels, roof, valu_roof, compute_roof, side = {}, None, None, None, None
     staged_mode = not args.inputs_in_kernel
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         eng.profile(True)
         for i in range(args.steps):
             step(base + args.steps + i, args.inputs_in_kernel, 1)
@@ -633,7 +700,7 @@ def main():
                         "once and read once): moved by the LEVELS engine, NOT by this kernel; a "
                         "comparison figure only"}
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         # this rank's timed steps: trials [first_of(i), first_of(i) + B) for i in the
         # timed slots (contiguous at world 1); checked against its pre-all-reduce counters
         cpu = run_cpu_baseline(n, m, args.seed, fmax, args.cpu_budget_s,
@@ -655,33 +722,41 @@ def main():
             "inputs": "in-kernel Philox draws" if args.inputs_in_kernel else
                       "staged in HBM before the timed region (ba_gen_inputs_device); lies drawn in-kernel",
             "schedule": (f"step i on stream/ctx i % {NS}: up to {NS} steps in flight, each a full "
-                         "1M-trial pass with its own outputs; every step's counters summed and checked"
+                         "1M-trial pass with its own outputs; every step's counters summed" +
+                         (" and checked" if args.full else "")
                          if NS > 1 else "one step at a time on one stream"),
             "ms_per_step_gpu_events": round(gpu_ms / args.steps, 4),
             "host_enqueue_ms_per_step": round(enq_ms / args.steps, 4),
             "value_gpu_events": round(B * args.steps / (gpu_ms * 1e-3), 1),
             "streams": NS,
-            "value_single_stream": round(value_1, 1),
-            "ms_per_step_single_stream_gpu_events": round(gpu_ms_1 / args.steps, 4),
-            "value_with_input_generation": round(value_gen, 1) if value_gen else None,
-            "ms_per_step_with_input_generation_gpu_events": round(gen_ms / args.steps, 4) if gen_ms else None,
             "warm_up_s": round(warm_s, 2),
-            "sclk_mhz_timed": sclk,
-            "clock": {"sclk_mhz_median_xcd": sclk, "per_xcd_mhz": {str(k): v for k, v in sclk_xcd.items()},
-                      "ms_per_step_gpu_events_clock_pass": round(gpu_ms_c / args.steps, 4),
-                      "value_at_2400mhz": round(value * 2400.0 / sclk, 1) if sclk else None,
-                      "note": "engine clock over a replica of the timed region (same steps, streams "
-                              "and schedule, untimed), from two s_memtime/s_memrealtime probes "
-                              "bracketing it (ba_clock_probe_device); value_at_2400mhz = value x "
-                              "2400 / sclk: a labelled side figure, not a measurement"},
-            "kernels_ms": {k: round(v[1] / v[0], 4) for k, v in kernels.items()},
-            "roofline": roof,
-            "valu_roofline": valu_roof,
-            "compute_roofline": compute_roof,
-            "level_synchronous_equivalent": side,
-            "cpu_baseline": cpu,
-            "counters": counters,
+            "full": args.full,
+            "outputs_dumped": {"dir": args.dump_outputs, "files": dumped} if dumped else None,
         }
+        if args.full:  # the side measurements, each from a pass of its own
+            line.update({
+                "value_single_stream": round(value_1, 1),
+                "ms_per_step_single_stream_gpu_events": round(gpu_ms_1 / args.steps, 4),
+                "value_with_input_generation": round(value_gen, 1) if value_gen else None,
+                "ms_per_step_with_input_generation_gpu_events":
+                    round(gen_ms / args.steps, 4) if gen_ms else None,
+                "sclk_mhz_timed": sclk,
+                "clock": {"sclk_mhz_median_xcd": sclk,
+                          "per_xcd_mhz": {str(k): v for k, v in sclk_xcd.items()},
+                          "ms_per_step_gpu_events_clock_pass": round(gpu_ms_c / args.steps, 4),
+                          "value_at_2400mhz": round(value * 2400.0 / sclk, 1) if sclk else None,
+                          "note": "engine clock over a replica of the timed region (same steps, streams "
+                                  "and schedule, untimed), from two s_memtime/s_memrealtime probes "
+                                  "bracketing it (ba_clock_probe_device); value_at_2400mhz = value x "
+                                  "2400 / sclk: a labelled side figure, not a measurement"},
+                "kernels_ms": {k: round(v[1] / v[0], 4) for k, v in kernels.items()},
+                "roofline": roof,
+                "valu_roofline": valu_roof,
+                "compute_roofline": compute_roof,
+                "level_synchronous_equivalent": side,
+                "cpu_baseline": cpu,
+            })
+        line["counters"] = counters
         print(json.dumps(line), flush=True)
     if comm is not None:
         comm.close()

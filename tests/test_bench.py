@@ -178,6 +178,51 @@ def test_cpu_baseline_world2_gloo():
     assert q.get(timeout=5) is True
 
 
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: the uint64 decision words come back exactly from their two
+    32-bit halves, the outcome bytes and counters unchanged, all as float32/float64."""
+    import numpy as np
+    B, first = 1000, 7 * 1000
+    dec = (np.arange(B, dtype=np.uint64) << np.uint64(31)) | np.uint64(0x2A5)
+    dec[-1] = np.uint64(0xFFFFFFFFFFFFFFFF)
+    out = (np.arange(B) % 5).astype(np.uint8)
+    cnt = np.arange(16, dtype=np.int64) << 40
+    d = tmp_path / "dump"
+    files = bench.dump_outputs(str(d), dec.view(np.int64), out, cnt, first)
+    assert sorted(files) == sorted(os.listdir(d)) and "decisions_lo.npy" in files
+    got = {f[:-4]: np.load(d / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    words = (got["decisions_hi"].astype(np.uint64) << np.uint64(32)) | got["decisions_lo"].astype(np.uint64)
+    assert np.array_equal(words, dec)
+    assert np.array_equal(got["outcome"], out) and np.array_equal(got["counters"], cnt)
+    assert np.array_equal(got["trial_index"], first + np.arange(B))
+    files = bench.dump_outputs(str(d), dec, out, cnt, first, "_rank3")
+    assert "outcome_rank3.npy" in files and len(os.listdir(d)) == 2 * len(files)
+
+
+def test_dump_outputs_samples_a_large_step(tmp_path, monkeypatch):
+    """A step too large for the size limit is written as a fixed sample: the same
+    ascending trials on every call, within the limit, values taken at those trials."""
+    import numpy as np
+    B, first, keep = 5000, 64, 300
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", (1 << 16) + keep * bench.DUMP_TRIAL_BYTES)
+    dec = np.arange(B, dtype=np.uint64) * np.uint64(0x100000001)
+    out = (np.arange(B) % 251).astype(np.uint8)
+    cnt = np.zeros(16, dtype=np.int64)
+    got = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        files = bench.dump_outputs(str(d), dec, out, cnt, first)
+        assert sum(os.path.getsize(d / f) for f in files) <= bench.DUMP_MAX_BYTES
+        got.append({f[:-4]: np.load(d / f) for f in files})
+    a, b = got
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    idx = a["trial_index"].astype(np.int64) - first
+    assert len(idx) == keep and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < B
+    assert np.array_equal(a["decisions_lo"], idx) and np.array_equal(a["decisions_hi"], idx)
+    assert np.array_equal(a["outcome"], out[idx])
+
+
 def test_clock_from_probes_pairs_rows_by_cu():
     """The engine clock per XCD comes from rows of the same XCD, shader engine and CU
     (HW_ID bits 8-15) in the two probes; an unrelated CU's counter (another engine's

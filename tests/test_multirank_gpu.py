@@ -166,7 +166,7 @@ def test_bench_two_ranks_through_library_collectives(tmp_path):
                FAKE_RCCL_TIMEOUT_S="90", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, os.path.join(MR.ROOT, "bench.py"), "--gpus", "2",
                         "--steps", str(steps), "--warmup", "1", "--batch", str(B), "--warm-s", "0.2",
-                        "--cpu-budget-s", "1", "--no-profile"],
+                        "--full", "--cpu-budget-s", "1", "--no-profile"],
                        env=env, capture_output=True, text=True, timeout=300, cwd=MR.ROOT)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
