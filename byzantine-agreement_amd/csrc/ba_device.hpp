@@ -184,7 +184,13 @@ struct KeysV {
 };
 
 // philox10_n with the round keys as VGPR operands (KeysV); same results.
-template <int G>
+// WIN: the register window of the asm statement's fixed product pairs
+// (ba_philox_asm.hpp: v[6G WIN, 6G (WIN + 1)), WIN = 0..3).  A group's y, w come
+// out in its window, so back-to-back groups that rotate through windows are
+// consumed where they land; in one window the compiler copies them out of the
+// next group's way.  A kernel that names window WIN allocates at least
+// 6G (WIN + 1) VGPRs: only k_om3w's rounds, far above that, use windows 1 to 3.
+template <int G, int WIN = 0>
 __device__ __forceinline__ void philox10_n_vk(P4 (&c)[G], const KeysV& kv) {
     static_for_h<0, 2>([&](auto i) {
         uint64_t p0[G], p1[G];
@@ -213,7 +219,10 @@ __device__ __forceinline__ void philox10_n_vk(P4 (&c)[G], const KeysV& kv) {
             z[g] = c[g].z;
             w[g] = c[g].w;
         }
-        philox_r29_asm_vkm<G>(x, y, z, w, rk0, rk1, kv.m0, kv.m1);
+        if constexpr (WIN == 0) philox_r29_asm_vkm<G>(x, y, z, w, rk0, rk1, kv.m0, kv.m1);
+        else if constexpr (WIN == 1) philox_r29_asm_vkm_w1<G>(x, y, z, w, rk0, rk1, kv.m0, kv.m1);
+        else if constexpr (WIN == 2) philox_r29_asm_vkm_w2<G>(x, y, z, w, rk0, rk1, kv.m0, kv.m1);
+        else philox_r29_asm_vkm_w3<G>(x, y, z, w, rk0, rk1, kv.m0, kv.m1);
 #pragma unroll
         for (int g = 0; g < G; ++g) c[g] = P4{x[g], y[g], z[g], w[g]};
     } else {
@@ -233,13 +242,13 @@ __device__ __forceinline__ void philox10_n_vk(P4 (&c)[G], const KeysV& kv) {
     }
 }
 
-template <int G>
+template <int G, int WIN = 0>
 __host__ __device__ __forceinline__ void philox10_n(P4 (&c)[G], uint32_t k0, uint32_t k1) {
 #if defined(__HIP_DEVICE_COMPILE__)
     // round keys as VGPR operands (KeysV, hoisted by the compiler): Philox calls
     // 8.4e11 -> 9.6e11 per second at 2 waves/SIMD (tools/philox_bench)
     if constexpr (G >= 2 && G <= 5) {
-        philox10_n_vk<G>(c, KeysV(k0, k1));
+        philox10_n_vk<G, WIN>(c, KeysV(k0, k1));
         return;
     }
 #endif
@@ -512,6 +521,17 @@ __device__ __forceinline__ uint64_t part1by1(uint32_t v) {
 // row (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror: four VALU
 // adds), then the four row sums by readlane -- where a __shfl_xor tree is six
 // dependent ds_bpermute round trips through LDS.
+// x + the value of the lane DPP control CTRL names, as one v_add_u32_dpp: with
+// old = 0 and bound_ctrl the DPP move folds into the add (wave_sum_u32's mov_dpp
+// with an undefined old value stays a v_mov_b32_dpp in front of it; k_om4w, the
+// one kernel still on wave_sum_u32, keeps that form: its spill counts are held
+// at what they are).  For controls under which every lane has a source lane
+// (quad_perm, row mirrors).
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_add(uint32_t x) {
+    return x + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, true);
+}
+
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t x) {
     x += (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, false);
     x += (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xF, 0xF, false);

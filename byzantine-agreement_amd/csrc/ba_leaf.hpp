@@ -69,7 +69,10 @@ struct LeafSched {
 
 // emit(b, R_b) receives column b's majority as soon as the column is complete
 // (a caller that stores it right away keeps no result registers live).
-template <int S, typename Emit>
+// WINS: the groups rotate through Philox register windows 1, 2, 3 (philox10_n),
+// starting in 1, so the carry-save code reads each group's lie words where the
+// asm left them while the next group runs; 0: every group in window 0.
+template <int S, bool WINS = false, typename Emit>
 __device__ __forceinline__ void leaf_block_cols(uint32_t me, uint64_t seed, uint64_t gw,
                                                 uint32_t sr, const uint64_t (&diag)[S],
                                                 const uint64_t (&Fm)[S], Emit&& emit) {
@@ -92,7 +95,7 @@ __device__ __forceinline__ void leaf_block_cols(uint32_t me, uint64_t seed, uint
 #endif
             c[g()] = P4{cx, me, (uint32_t)gw, (uint32_t)(gw >> 32)};
         });
-        philox10_n<ng>(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+        philox10_n<ng, (WINS ? 1 + grp() % 3 : 0)>(c, (uint32_t)seed, (uint32_t)(seed >> 32));
         static_for<0, ng>([&](auto g) {
             constexpr int t = t0 + g(), q = LeafSched::step_pair(S, t);
             static_for<0, 2>([&](auto h) {
@@ -150,13 +153,13 @@ __device__ __forceinline__ void leaf_block(uint32_t me, uint64_t seed, uint64_t 
 // leaf_block with the results handed to emit(b, R_b) (std::integral_constant b):
 // right when each column completes under the column schedule, at the end
 // otherwise.
-template <int S, typename Emit>
+template <int S, bool WINS = false, typename Emit>
 __device__ __forceinline__ void leaf_block_emit(uint32_t me, uint64_t seed, uint64_t gw,
                                                 uint32_t sr, const uint64_t (&diag)[S],
                                                 const uint64_t (&Fm)[S], Emit&& emit) {
 #ifndef BA_LEAF_ROW_ORDER
     if constexpr (S >= 3 && (S - 1) % 2 == 0) {
-        leaf_block_cols<S>(me, seed, gw, sr, diag, Fm, emit);
+        leaf_block_cols<S, WINS>(me, seed, gw, sr, diag, Fm, emit);
         return;
     }
 #endif

@@ -472,6 +472,42 @@ __device__ __forceinline__ void wave_fold(const TrialCounts& tc, uint32_t lane, 
     }
 }
 
+// The same fold with two counters per dword and no readlane (k_om3w).  A task is at most
+// 64 W trials and a trial adds at most N to any counter (faulty_total,
+// attack_total: one per general), so every wave sum is below 2^16 and counters
+// 2k, 2k+1 share dword k: C_NUM/2 row reductions of one v_add_u32_dpp per step
+// (update_dpp with old = 0 and bound_ctrl folds into the add; every lane of a
+// row has a source lane, so the old value never shows).  The four row sums of
+// every dword go through `scratch` (4 * C_NUM/2 dwords of the wave's LDS that no
+// lane reads or writes around the fold; the callers put wave barriers on both
+// sides): the row leaders store them, lane c reads its counter's four 16-bit
+// halves back.  Against wave_fold: 6 packs + 24 DPP adds + 5 adds, where the
+// twelve separate sums took 48 DPP moves, 47 adds, 48 readlanes and 12 selects.
+template <int N, int W>
+__device__ __forceinline__ void wave_fold_packed(const TrialCounts& tc, uint32_t lane,
+                                                 uint64_t* scratch, uint64_t& mine) {
+    static_assert(64 * W * N < 65536, "two task counters per dword: each wave sum must fit 16 bits");
+    static_assert(C_NUM % 2 == 0, "counters fold in pairs");
+    constexpr int NP = C_NUM / 2;
+    uint32_t p[NP];
+    static_for<0, NP>([&](auto k) { p[k()] = tc.v[2 * k()] | tc.v[2 * k() + 1] << 16; });
+    static_for<0, NP>([&](auto k) { p[k()] = dpp_add<0xB1>(p[k()]); });   // quad_perm [1,0,3,2]
+    static_for<0, NP>([&](auto k) { p[k()] = dpp_add<0x4E>(p[k()]); });   // quad_perm [2,3,0,1]
+    static_for<0, NP>([&](auto k) { p[k()] = dpp_add<0x141>(p[k()]); });  // row_half_mirror
+    static_for<0, NP>([&](auto k) { p[k()] = dpp_add<0x140>(p[k()]); });  // row_mirror
+    uint32_t* s32 = reinterpret_cast<uint32_t*>(scratch);
+    if ((lane & 15u) == 0) {
+        uint32_t* d = s32 + (lane >> 4) * NP;
+        static_for<0, NP>([&](auto k) { d[k()] = p[k()]; });
+    }
+    __builtin_amdgcn_wave_barrier();
+    if (lane < (uint32_t)C_NUM) {
+        const uint16_t* h = reinterpret_cast<const uint16_t*>(s32) + lane;
+        const uint32_t x = (uint32_t)h[0] + (uint32_t)h[2 * NP] + (uint32_t)h[4 * NP] + (uint32_t)h[6 * NP];
+        mine += x;
+    }
+}
+
 // Run counters of the block from the waves' folded sums: the waves combine in
 // LDS, then one sink unit per block.  Every wave of the block must call it (it
 // contains a block barrier).
@@ -541,6 +577,36 @@ __device__ __forceinline__ P4 sel_p4(bool c, const P4& a, const P4& b) {
 // __shfl_xor goes through ds_bpermute and waits out an LDS round trip).
 __device__ __forceinline__ uint32_t swap_pair(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, false);
+}
+
+// The pair exchange of om3_round's shared Philox group between lanes 2k (odd =
+// 0) and 2k + 1 (odd = 1), f / l the lane's first / last call:
+//   q       = odd ? l : f of lane ^ 1
+//   lie_lo  = odd ? l.z of lane ^ 1 : l.x      lie_hi = odd ? l.w of lane ^ 1 : l.y
+// v_cndmask_b32_dpp takes its DPP operand where VCC is clear, so VCC is the lane
+// parity for q and its complement for the lie word.  Both lanes of a pair are
+// active (the callers' lane counts are even).  The leading s_nop 1 are the two
+// wait states a DPP read needs after the VALU write of its source (the hazard
+// recognizer does not see into the statement).
+struct PairExchange {
+    P4 q;
+    uint32_t lie_lo, lie_hi;
+};
+__device__ __forceinline__ PairExchange pair_exchange(uint32_t odd, const P4& f, const P4& l) {
+    PairExchange r;
+    asm("s_nop 1\n\t"
+        "v_cmp_ne_u32_e32 vcc, 0, %14\n\t"
+        "v_cndmask_b32_dpp %0, %6, %10, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_cndmask_b32_dpp %1, %7, %11, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_cndmask_b32_dpp %2, %8, %12, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_cndmask_b32_dpp %3, %9, %13, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_cmp_eq_u32_e32 vcc, 0, %14\n\t"
+        "v_cndmask_b32_dpp %4, %12, %10, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+        "v_cndmask_b32_dpp %5, %13, %11, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+        : "=&v"(r.q.x), "=&v"(r.q.y), "=&v"(r.q.z), "=&v"(r.q.w), "=&v"(r.lie_lo), "=&v"(r.lie_hi)
+        : "v"(f.x), "v"(f.y), "v"(f.z), "v"(f.w), "v"(l.x), "v"(l.y), "v"(l.z), "v"(l.w), "v"(odd)
+        : "vcc");
+    return r;
 }
 
 // Per-lane byte offsets (EROW mode of om3_round): K small offsets packed one
@@ -661,30 +727,32 @@ __device__ __forceinline__ uint64_t om3_round(const uint64_t* in, uint64_t l0j1,
                 pc[qd()] = P4{l1 ? (sr >> 1) : d0 + qd(), l1 ? 1u : 2u, (uint32_t)gw,
                               (uint32_t)(gw >> 32)};
             });
-            philox10_n<NPD>(pc, (uint32_t)seed, (uint32_t)(seed >> 32));
-            // even lane sends its level-1 pair, odd lane its first level-2 pair
-            // (component-wise selects: a select of whole P4 values can become a
-            // dynamically indexed scratch array)
-            const P4 snd = sel_p4(odd, pc[0], pc[NPD - 1]);
-            P4 rcv;
-            rcv.x = swap_pair(snd.x);
-            rcv.y = swap_pair(snd.y);
-            rcv.z = swap_pair(snd.z);
-            rcv.w = swap_pair(snd.w);
-            const P4 p1 = sel_p4(odd, rcv, pc[NPD - 1]);
-            static_for<0, NPD>([&](auto qd) {
-                const P4 q = qd() == NPD - 1 ? sel_p4(odd, pc[qd()], rcv) : pc[qd()];
-                lw2[2 * qd()] = (uint64_t)q.y << 32 | q.x;
-                lw2[2 * qd() + 1] = (uint64_t)q.w << 32 | q.z;
+            // (register window 3: the leaf block's groups follow in windows 1, 2, 3, 1, ...)
+            philox10_n<NPD, 3>(pc, (uint32_t)seed, (uint32_t)(seed >> 32));
+            // The exchange, one v_cndmask_b32_dpp per dword (select and lane ^ 1
+            // permute at once; sel_p4 / swap_pair / sel_p4 took 12 selects and 4
+            // DPP moves):
+            //   last level-2 pair: the odd lane's own last call, the even lane's
+            //                      partner's first call;
+            //   level-1 lie word:  the even lane's own last call's first half (sr
+            //                      even), the odd lane's partner's last call's
+            //                      second half (sr odd).
+            const P4 &f = pc[0], &l = pc[NPD - 1];
+            const PairExchange x = pair_exchange(odd ? 1u : 0u, f, l);
+            static_for<0, NPD - 1>([&](auto qd) {
+                lw2[2 * qd()] = (uint64_t)pc[qd()].y << 32 | pc[qd()].x;
+                lw2[2 * qd() + 1] = (uint64_t)pc[qd()].w << 32 | pc[qd()].z;
             });
-            lie = odd ? ((uint64_t)p1.w << 32 | p1.z) : ((uint64_t)p1.y << 32 | p1.x);
+            lw2[2 * NPD - 2] = (uint64_t)x.q.y << 32 | x.q.x;
+            lw2[2 * NPD - 1] = (uint64_t)x.q.w << 32 | x.q.z;
+            lie = (uint64_t)x.lie_hi << 32 | x.lie_lo;
         } else {
             P4 pc[NPD + 1];
             static_for<0, NPD>([&](auto qd) {
                 pc[qd()] = P4{(x0 >> 1) + qd(), 2u, (uint32_t)gw, (uint32_t)(gw >> 32)};
             });
             pc[NPD] = P4{sr >> 1, 1u, (uint32_t)gw, (uint32_t)(gw >> 32)};
-            philox10_n<NPD + 1>(pc, (uint32_t)seed, (uint32_t)(seed >> 32));
+            philox10_n<NPD + 1, 3>(pc, (uint32_t)seed, (uint32_t)(seed >> 32));
             static_for<0, NPD>([&](auto qd) {
                 lw2[2 * qd()] = (uint64_t)pc[qd()].y << 32 | pc[qd()].x;
                 lw2[2 * qd() + 1] = (uint64_t)pc[qd()].w << 32 | pc[qd()].z;
@@ -705,7 +773,7 @@ __device__ __forceinline__ uint64_t om3_round(const uint64_t* in, uint64_t l0j1,
         // receiver-major: member d of block a is receiver b = d + (d >= a)
         uint64_t* r2t = r2t_w + lw * C * CP + la;
         char* rb = (char*)r2t;
-        leaf_block_emit<S>(ME, seed, gw, sr, diag, Fm, [&](auto d, uint64_t v) {
+        leaf_block_emit<S, true>(ME, seed, gw, sr, diag, Fm, [&](auto d, uint64_t v) {
             if constexpr (BA_OM3W_LAB_NO_R2T) {  // lab ablation (wrong results): PMC attribution only
                 asm volatile("" ::"v"(v));
             } else if constexpr (EROW) {
@@ -920,12 +988,16 @@ __global__ __launch_bounds__(kWaveThreads, BA_OM3W_MIN_BLOCKS(N)) void k_om3w(
             TrialCounts tc;
             wave_epilogue<N, W, ME, DIAG>(img + G::oIN, img + G::oAU, lane, w0, batch, decisions,
                                           outcome, tc);
-            wave_fold(tc, lane, folded);
+            // (L0 is dead after the rounds: the fold's scratch)
+            wave_fold_packed<N, W>(tc, lane, img + G::oL0, folded);
         }
         __builtin_amdgcn_wave_barrier();
         FUSED_STAMP(4);
     }
-    wave_flush_folded(folded, threadIdx.x & 63, wv, wpb, counters, sk, (DIAG & 4) != 0);
+    // (the lane index from mbcnt, as in the task loop: threadIdx.x kept live
+    // across the whole kernel costs the rounds a VGPR)
+    wave_flush_folded(folded, __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), wv,
+                      wpb, counters, sk, (DIAG & 4) != 0);
 #ifdef BA_FUSED_STAMPS
     if ((threadIdx.x & 63) == 0 && blockIdx.x * wpb + wv < (uint32_t)kPartialRows)
     {
@@ -1218,6 +1290,8 @@ __global__ __launch_bounds__(kWaveThreads, BA_OM4W_BLOCKS_PER_CU) void k_om4w(
         {
             TrialCounts tc;
             wave_epilogue<N, W, ME, 0>(img + G::oIN, img + G::oAU, lane, w0, batch, decisions, outcome, tc);
+            // (wave_fold_packed here costs every k_om4w variant 1-7 more spilled
+            // VGPRs at its 168-VGPR bound: the one-counter fold stays)
             wave_fold(tc, lane, folded);
         }
         __builtin_amdgcn_wave_barrier();

@@ -16,6 +16,10 @@ it writes the next ones); the final y, w are bound to the low halves of the
 last round's pairs through physical-register output constraints.  The fixed
 registers start at v[BASE]; every kernel already uses more than 8G VGPRs, so
 the allocator only has to keep its other values out of them across the asm.
+Every group size is also emitted in register windows 1 to 3 (philox_r29_asm_vkm_w1
+.. _w3: the fixed pairs at v[6G w, 6G (w + 1))).  k_om3w's rounds rotate their
+groups through them, so the next statements do not overwrite a group's y, w
+before the carry-save code has read them (tests/test_philox_asm_windows.py).
 
 Round i (products p0 = M0*x, p1 = M1*z; Salmon et al. 2011, the same algebra as
 ba_device.hpp philox10):
@@ -40,7 +44,9 @@ MODE = os.environ.get("PHILOX_ASM_MODE", "rot")  # "rot": 3 pairs per call; "pai
 NCC = int(os.environ.get("PHILOX_ASM_NCC", "1"))
 
 
-def gen(G: int, kc: str = "s", mc: str = "s") -> str:
+def gen(G: int, kc: str = "s", mc: str = "s", win: int = 0) -> str:
+    # win: the register window of the fixed pairs, v[6G*win .. 6G*(win+1)) ("rot" mode)
+    base = BASE + 6 * G * win
     # operand numbering: outputs first (x[g], z[g] in/out; w[g], y[g] fixed), then
     # inputs (y_in[g], w_in[g], keys k0[0..7], k1[0..7], M0, M1), cc last output
     ops_out, ops_in = [], []
@@ -95,7 +101,7 @@ def gen(G: int, kc: str = "s", mc: str = "s") -> str:
         # per round: fr <- x*M0, (x reg) <- z' = hi(fr)^w^k1, pw <- z*M1 (pw is
         # free once its w is read), (z reg) <- x' = hi(pw)^y^k0; the x and z
         # registers swap roles every round (8 rounds: back in place)
-        pairs = [[BASE + 6 * g + 2 * j for j in range(3)] for g in range(G)]
+        pairs = [[base + 6 * g + 2 * j for j in range(3)] for g in range(G)]
         free = [list(pairs[g]) for g in range(G)]
         pw, py = [None] * G, [None] * G
         xr = [f"%{X(g)}" for g in range(G)]
@@ -155,6 +161,9 @@ def gen(G: int, kc: str = "s", mc: str = "s") -> str:
     text = [l + ("\\n\\t" if k + 1 < len(lines) else "") for k, l in enumerate(lines)]
     body = "\n".join('        "' + "".join(text[k:k + G]) + '"' for k in range(0, len(text), G))
     fname = "philox_r29_asm" if kc == "s" else ("philox_r29_asm_vk" if mc == "s" else "philox_r29_asm_vkm")
+    if win:
+        assert MODE == "rot" and fname == "philox_r29_asm_vkm"
+        fname += f"_w{win}"
     mparams = "" if mc == "s" else ",\n                                                 uint32_t m0, uint32_t m1"
     return f"""template <>
 __device__ __forceinline__ void {fname}<{G}>(uint32_t (&x)[{G}], uint32_t (&y)[{G}],
@@ -204,6 +213,27 @@ def main():
             '                                                   uint32_t (&z)[G], uint32_t (&w)[G],',
             '                                                   const uint32_t (&k0)[8], const uint32_t (&k1)[8],',
             '                                                   uint32_t m0, uint32_t m1);',
+            '// The same in register windows 1 to 3, v[6G w, 6G (w + 1)).  A group\'s',
+            '// y, w come out in low halves of its fixed pairs, and the next statement in the',
+            '// same window overwrites them: the compiler copies them away first (24 v_mov per',
+            '// k_om3w<10> round).  Consecutive groups that rotate through windows leave each',
+            '// other\'s outputs where they landed; windows 1 to 3 also keep clear of v0..,',
+            '// where the allocator puts the short-lived values between two groups.',
+            'template <int G>',
+            '__device__ __forceinline__ void philox_r29_asm_vkm_w1(uint32_t (&x)[G], uint32_t (&y)[G],',
+            '                                                      uint32_t (&z)[G], uint32_t (&w)[G],',
+            '                                                      const uint32_t (&k0)[8], const uint32_t (&k1)[8],',
+            '                                                      uint32_t m0, uint32_t m1);',
+            'template <int G>',
+            '__device__ __forceinline__ void philox_r29_asm_vkm_w2(uint32_t (&x)[G], uint32_t (&y)[G],',
+            '                                                      uint32_t (&z)[G], uint32_t (&w)[G],',
+            '                                                      const uint32_t (&k0)[8], const uint32_t (&k1)[8],',
+            '                                                      uint32_t m0, uint32_t m1);',
+            'template <int G>',
+            '__device__ __forceinline__ void philox_r29_asm_vkm_w3(uint32_t (&x)[G], uint32_t (&y)[G],',
+            '                                                      uint32_t (&z)[G], uint32_t (&w)[G],',
+            '                                                      const uint32_t (&k0)[8], const uint32_t (&k1)[8],',
+            '                                                      uint32_t m0, uint32_t m1);',
             '']
     out.append('#ifdef __HIP_DEVICE_COMPILE__  // device code only (host passes never call it)')
     if lab:
@@ -213,6 +243,9 @@ def main():
             out.append(gen(G, "v"))
     for G in GS:
         out.append(gen(G, "v", "v"))
+    for win in (1, 2, 3):
+        for G in GS:
+            out.append(gen(G, "v", "v", win))
     out.append('#endif')
     out.append('}  // namespace ba')
     print("\n".join(out))
