@@ -154,6 +154,46 @@ __host__ __device__ __forceinline__ P4 philox10(P4 c, uint32_t k0, uint32_t k1) 
     return c;
 }
 
+// Rounds 0-1 of a lie call, counter {pair, level, gw_lo, gw_hi}, split by what
+// each part depends on (k_om3wt's pair table; tests/native/philox_split_check.cpp
+// holds the three helpers to philox10 on the host):
+//   round 0:  p0 = M0 pair              p1 = M1 gw_lo
+//             x1 = hi(p1) ^ level ^ k0   y1 = lo(p1)
+//             z1 = hi(p0) ^ gw_hi ^ k1   w1 = lo(p0)
+//   round 1:  p0' = M0 x1               p1' = M1 z1
+//             x2 = hi(p1') ^ y1 ^ k0'    y2 = lo(p1')
+//             z2 = hi(p0') ^ w1 ^ k1'    w2 = lo(p0')
+// w1, hi(p1'), lo(p1') depend on (pair, gw_hi, key) only: the lanes of a wave
+// that hold the same leaf block of different trial words share them.  y1 ^ k0',
+// hi(p0') ^ k1' and w2 depend on (level, gw_lo, key) only: one set per lane.  What
+// is left per call is two 2-input xors.
+struct PhiloxPairEntry {
+    uint32_t w1, h, l;  // lo(M0 pair), hi(p1'), lo(p1')
+};
+struct PhiloxWordConsts {
+    uint32_t a, b, w2;  // y1 ^ k0', hi(p0') ^ k1', lo(p0')
+};
+__host__ __device__ __forceinline__ PhiloxPairEntry philox_pair_entry(uint32_t pair, uint32_t gw_hi,
+                                                                      uint32_t k1) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * pair;
+    const uint32_t z1 = xor3_32((uint32_t)(p0 >> 32), gw_hi, k1);
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * z1;
+    return PhiloxPairEntry{(uint32_t)p0, (uint32_t)(p1 >> 32), (uint32_t)p1};
+}
+__host__ __device__ __forceinline__ PhiloxWordConsts philox_word_consts(uint32_t level, uint32_t gw_lo,
+                                                                        uint32_t k0, uint32_t k1) {
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * gw_lo;
+    const uint32_t x1 = xor3_32((uint32_t)(p1 >> 32), level, k0);
+    const uint64_t p0 = (uint64_t)0xD2511F53u * x1;
+    return PhiloxWordConsts{(uint32_t)p1 ^ (k0 + 0x9E3779B9u), (uint32_t)(p0 >> 32) ^ (k1 + 0xBB67AE85u),
+                            (uint32_t)p0};
+}
+// the call's state after round 1
+__host__ __device__ __forceinline__ P4 philox_finish01(const PhiloxPairEntry& e,
+                                                       const PhiloxWordConsts& c) {
+    return P4{e.h ^ c.a, e.l, e.w1 ^ c.b, c.w2};
+}
+
 // G independent Philox4x32-10 calls advanced round by round in lockstep: the
 // source order interleaves the chains, so each v_mad_u64_u32 result is used G
 // instructions later instead of right away (left to itself the scheduler runs
@@ -267,6 +307,35 @@ __host__ __device__ __forceinline__ void philox10_n(P4 (&c)[G], uint32_t k0, uin
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
     });
+}
+
+// Rounds 2-9 of G = 2..5 interleaved calls whose state after round 1 is c
+// (philox_finish01): the tail of philox10_n_vk, same statements and windows.
+template <int G, int WIN = 0>
+__device__ __forceinline__ void philox10_n_from2(P4 (&c)[G], uint32_t k0, uint32_t k1) {
+    static_assert(G >= 2 && G <= 5, "the generated statements cover groups of 2 to 5 calls");
+#if defined(__HIP_DEVICE_COMPILE__)  // (the statements exist in device passes only)
+    const KeysV kv(k0, k1);
+    uint32_t rk0[8], rk1[8], x[G], y[G], z[G], w[G];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        rk0[i] = kv.k0[i + 2];
+        rk1[i] = kv.k1[i + 2];
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        x[g] = c[g].x;
+        y[g] = c[g].y;
+        z[g] = c[g].z;
+        w[g] = c[g].w;
+    }
+    if constexpr (WIN == 0) philox_r29_asm_vkm<G>(x, y, z, w, rk0, rk1, kv.m0, kv.m1);
+    else if constexpr (WIN == 1) philox_r29_asm_vkm_w1<G>(x, y, z, w, rk0, rk1, kv.m0, kv.m1);
+    else if constexpr (WIN == 2) philox_r29_asm_vkm_w2<G>(x, y, z, w, rk0, rk1, kv.m0, kv.m1);
+    else philox_r29_asm_vkm_w3<G>(x, y, z, w, rk0, rk1, kv.m0, kv.m1);
+#pragma unroll
+    for (int g = 0; g < G; ++g) c[g] = P4{x[g], y[g], z[g], w[g]};
+#endif
 }
 
 // G calls as consecutive groups of at most 4 interleaved calls (sizes as even as

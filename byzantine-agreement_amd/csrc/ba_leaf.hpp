@@ -72,16 +72,68 @@ struct LeafSched {
 // WINS: the groups rotate through Philox register windows 1, 2, 3 (philox10_n),
 // starting in 1, so the carry-save code reads each group's lie words where the
 // asm left them while the next group runs; 0: every group in window 0.
-template <int S, bool WINS = false, typename Emit>
+// TAB (k_om3wt): a pair table (Om3PairTable, ba_wave.hpp) holds the pair-only
+// half of rounds 0-1 of every call of the block, S steps (one chunk) per slot of
+// a two-slot ring: tab->load<t>() is step t's entry, tab->build<k>() writes
+// chunk k over chunk k - 2.  A group's entries are loaded right after the
+// previous group's Philox statement, so the LDS latency hides under that group's
+// carry-save code, and chunk k >= 2 is built at the first group by which every
+// entry of chunk k - 2 has been loaded.  The call is then philox_finish01 (two
+// xors) and rounds 2-9 in the same statements and windows.  nullptr_t: as before.
+template <int S, bool WINS = false, typename Emit, typename Tab = std::nullptr_t>
 __device__ __forceinline__ void leaf_block_cols(uint32_t me, uint64_t seed, uint64_t gw,
                                                 uint32_t sr, const uint64_t (&diag)[S],
-                                                const uint64_t (&Fm)[S], Emit&& emit) {
+                                                const uint64_t (&Fm)[S], Emit&& emit,
+                                                Tab tab = nullptr) {
     constexpr int NL = planes_c(S);
     constexpr int NPAIR = S * (S - 1) / 2;
     constexpr int PG = leaf_philox_group(NPAIR);
+    constexpr bool TAB = !std::is_same<Tab, std::nullptr_t>::value;
     Csa<NL> cnt[S];
     static_for<0, S>([&](auto b) { cnt[b()].template add<0>(diag[b()]); });
     const uint32_t pair0 = sr * (uint32_t)NPAIR;
+    if constexpr (TAB) {
+        constexpr int NG = NPAIR / PG, NCH = (S - 1) / 2;
+        static_assert(NPAIR % PG == 0 && PG >= 2 && PG <= 5, "whole groups of the generated statements");
+        PhiloxPairEntry ent[PG];
+        static_for<0, PG>([&](auto g) { ent[g()] = tab->template load<g()>(); });
+        static_for<0, NG>([&](auto grp) {
+            constexpr int t0 = grp() * PG;
+            // chunk k over chunk k - 2: its last step S (k - 1) - 1 belongs to a group
+            // before this one (loaded), and chunk k's first step S k to a later one
+            static_for<2, NCH>([&](auto k) {
+                constexpr int gb = (S * (k() - 1) - 1) / PG + 1;
+                static_assert(gb <= S * k() / PG - 1 || S * k() / PG == 0, "ring of two chunks");
+                if constexpr (gb == grp()) {
+                    __builtin_amdgcn_wave_barrier();
+                    tab->template build<k()>();
+                    __builtin_amdgcn_wave_barrier();
+                }
+            });
+            P4 c[PG];
+            static_for<0, PG>([&](auto g) { c[g()] = philox_finish01(ent[g()], tab->wc); });
+            philox10_n_from2<PG, (WINS ? 1 + grp() % 3 : 0)>(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+            if constexpr (grp() + 1 < NG)
+                static_for<0, PG>([&](auto g) { ent[g()] = tab->template load<t0 + PG + g()>(); });
+            static_for<0, PG>([&](auto g) {
+                constexpr int t = t0 + g(), q = LeafSched::step_pair(S, t);
+                static_for<0, 2>([&](auto h) {
+                    constexpr int e = 2 * q + h();
+                    constexpr int a = e / (S - 1);
+                    constexpr int b = LeafSched::slot_recv(S, e);
+                    constexpr int K = LeafSched::inputs_before(S, b, t, h());
+                    const uint64_t lw = h() == 0 ? ((uint64_t)c[g()].y << 32 | c[g()].x)
+                                                 : ((uint64_t)c[g()].w << 32 | c[g()].z);
+                    cnt[b].template add<K>((Fm[a] & lw) | (~Fm[a] & diag[a]));
+                });
+                static_for<0, S>([&](auto b) {
+                    if constexpr (LeafSched::last_step(S, b()) == t)
+                        emit(b, cnt[b()].template ge<S, S / 2 + 1>());
+                });
+            });
+        });
+        return;
+    }
     static_for<0, (NPAIR + PG - 1) / PG>([&](auto grp) {
         constexpr int t0 = grp() * PG, ng = NPAIR - t0 < PG ? NPAIR - t0 : PG;
         P4 c[ng];
@@ -153,16 +205,18 @@ __device__ __forceinline__ void leaf_block(uint32_t me, uint64_t seed, uint64_t 
 // leaf_block with the results handed to emit(b, R_b) (std::integral_constant b):
 // right when each column completes under the column schedule, at the end
 // otherwise.
-template <int S, bool WINS = false, typename Emit>
+template <int S, bool WINS = false, typename Emit, typename Tab = std::nullptr_t>
 __device__ __forceinline__ void leaf_block_emit(uint32_t me, uint64_t seed, uint64_t gw,
                                                 uint32_t sr, const uint64_t (&diag)[S],
-                                                const uint64_t (&Fm)[S], Emit&& emit) {
+                                                const uint64_t (&Fm)[S], Emit&& emit,
+                                                Tab tab = nullptr) {
 #ifndef BA_LEAF_ROW_ORDER
     if constexpr (S >= 3 && (S - 1) % 2 == 0) {
-        leaf_block_cols<S, WINS>(me, seed, gw, sr, diag, Fm, emit);
+        leaf_block_cols<S, WINS>(me, seed, gw, sr, diag, Fm, emit, tab);
         return;
     }
 #endif
+    // (a pair table needs the column schedule: Om3PairTable asserts an odd S)
     uint64_t R[S];
     leaf_block<S>(me, seed, gw, sr, diag, Fm, R);
     static_for<0, S>([&](auto b) { emit(b, R[b()]); });

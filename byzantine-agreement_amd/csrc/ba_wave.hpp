@@ -670,6 +670,62 @@ struct Om3LaneOffsets {
     }
 };
 
+// The pair table of k_om3wt (leaf_block_cols TAB mode; the split itself:
+// ba_device.hpp, philox_pair_entry).  A leaf call's pair is (j1 C + la) NPAIR + q:
+// the W lanes (w, la) that hold leaf block la of W different trial words draw the
+// same pairs, so the pair-only half of rounds 0-1 is computed once per wave and
+// read back by every lane.  Chunk k = steps S k .. S k + S - 1 of the column
+// schedule, whose pairs are step_pair(S, S k + w) = w (S-1)/2 + k: lane (w, la)
+// builds entry (block la, step S k + min(w, S - 1)) in one pass (every lane, so
+// the round stays one straight-line block: the lanes w >= S repeat lane S - 1's
+// entry, same value to the same address).  Per wave, two chunk slots of C rows
+// (one per leaf block) of ROW bytes: S x {hi(p1'), lo(p1')} as 8-byte words, then
+// S x w1 as dwords, padded to 8 bytes.  For n = 10 the row is 88 bytes = 22
+// dwords: a read is 8 distinct addresses (one per la, each broadcast to the 8
+// lanes of that block), and 22 la mod 64 (ds_read_b64, two banks each) and mod 32
+// (ds_read_b32, ds_read2_b64) are distinct: conflict-free (banks_distinct below;
+// tools/lds_bank_model.py --table).  One wave's LDS operations complete in
+// order, so an entry written before the wave barrier is what every lane reads
+// after it.
+template <int N>
+struct Om3PairTable {
+    static constexpr int S = N - 3, C = N - 2, W = 64 / C, NPAIR = S * (S - 1) / 2;
+    static constexpr int NCH = (S - 1) / 2;  // chunks per round = pairs per row of the block
+    static constexpr int ROW = (12 * S + 7) / 8 * 8, SLOT = C * ROW;
+    static constexpr int words = 2 * SLOT / 8;
+    static_assert(S % 2 == 1 && S >= 3 && W >= S && W * C == 64, "one builder lane per (block, step of a chunk)");
+    // the C rows' first dwords on distinct banks mod 32 (ds_read_b32) and distinct
+    // bank pairs mod 64 (ds_read_b64)
+    static constexpr bool banks_distinct() {
+        for (int a = 0; a < C; ++a)
+            for (int b = a + 1; b < C; ++b) {
+                const int d = (b - a) * (ROW / 4);
+                if (d % 32 == 0 || d % 64 == 0 || d % 64 == 1 || d % 64 == 63) return false;
+            }
+        return ROW % 8 == 0;
+    }
+    static_assert(banks_distinct(), "pair table rows: conflict-free reads");
+    char* row;            // this lane's block row in slot 0
+    uint32_t bw;          // builder: the step of the chunk, min(the lane's word index, S - 1)
+    uint32_t pair0;       // builder: pair of chunk 0's entry, sr NPAIR + bw NCH
+    uint32_t gw_hi, k1;   // the launch's upper word half, the round-0 key
+    PhiloxWordConsts wc;  // the lane's own word at the leaf level
+    template <int K>
+    __device__ __forceinline__ void build() const {
+        const PhiloxPairEntry e = philox_pair_entry(pair0 + K, gw_hi, k1);
+        char* p = row + (K & 1) * SLOT;
+        *(uint64_t*)(p + 8 * bw) = (uint64_t)e.l << 32 | e.h;
+        *(uint32_t*)(p + 8 * S + 4 * bw) = e.w1;
+    }
+    template <int T>
+    __device__ __forceinline__ PhiloxPairEntry load() const {
+        constexpr int k = T / S, s = T % S;
+        const char* p = row + (k & 1) * SLOT;
+        const uint64_t hl = *(const uint64_t*)(p + 8 * s);
+        return PhiloxPairEntry{*(const uint32_t*)(p + 8 * S + 4 * s), (uint32_t)hl, (uint32_t)(hl >> 32)};
+    }
+};
+
 // EROW = true (k_om3w, rounds in order j1 = 0, 1, ...): the members' faulty
 // words come from the word's E row (erow: E[lw][0..C], E[C] a spare slot):
 // E = the lieutenants other than j1 in rank order, which moves by ONE entry per
@@ -677,19 +733,35 @@ struct Om3LaneOffsets {
 // la == j1 write it, after this round's reads).  One byte extract + add per
 // member instead of two rank compares, selects and shifts.  EROW = false
 // (lab k_om3q: rounds in any order) ranks the members from j1 and j2 each round.
-template <int N, bool EROW = false>
+// Tab = const Om3PairTable<N>* (k_om3wt): the leaf calls take the pair-only half
+// of their rounds 0-1 from the wave's pair table (pair0 is set here per round).
+template <int N, bool EROW = false, typename Tab = std::nullptr_t>
 __device__ __forceinline__ uint64_t om3_round(const uint64_t* in, uint64_t l0j1, uint64_t* r2t_w,
                                               uint32_t lw, uint32_t la, bool act, uint32_t j1,
                                               uint64_t seed, uint64_t gw,
                                               uint64_t* erow = nullptr,
-                                              const Om3LaneOffsets<N>* lo_ = nullptr) {
+                                              const Om3LaneOffsets<N>* lo_ = nullptr,
+                                              Tab tab_ = nullptr) {
     constexpr int L = N - 1, S = N - 3, C = L - 1, CP = C + BA_OM3W_R2T_PAD;
     constexpr uint32_t ME = 3;
     const uint32_t sr = j1 * C + la;             // level-1 slot (j1, j2)
     const uint32_t j2 = la + (la >= j1);
     Om3LaneOffsets<N> ofs(0u);
     if constexpr (EROW) ofs = lo_->round_copy();
+    constexpr bool TAB = !std::is_same<Tab, std::nullptr_t>::value;
+    [[maybe_unused]] std::conditional_t<TAB, Om3PairTable<N>, int> tab{};
+    if constexpr (TAB) {
+        // chunks 0 and 1 of this round's table (the previous round's last loads were
+        // issued before its column reads; one wave's LDS operations complete in order)
+        tab = *tab_;
+        tab.pair0 = sr * (uint32_t)tab.NPAIR + tab.bw * (uint32_t)tab.NCH;
+    }
     if (act) {
+        if constexpr (TAB) {
+            tab.template build<0>();
+            tab.template build<1>();
+            __builtin_amdgcn_wave_barrier();
+        }
         // the round's input planes, loaded before the Philox group so their
         // LDS latency hides under it: F[j1] (level-1 sender), F[j2] (level-2
         // sender) and the faulty words of the block's S members
@@ -773,7 +845,7 @@ __device__ __forceinline__ uint64_t om3_round(const uint64_t* in, uint64_t l0j1,
         // receiver-major: member d of block a is receiver b = d + (d >= a)
         uint64_t* r2t = r2t_w + lw * C * CP + la;
         char* rb = (char*)r2t;
-        leaf_block_emit<S, true>(ME, seed, gw, sr, diag, Fm, [&](auto d, uint64_t v) {
+        auto emit = [&](auto d, uint64_t v) {
             if constexpr (BA_OM3W_LAB_NO_R2T) {  // lab ablation (wrong results): PMC attribution only
                 asm volatile("" ::"v"(v));
             } else if constexpr (EROW) {
@@ -781,7 +853,9 @@ __device__ __forceinline__ uint64_t om3_round(const uint64_t* in, uint64_t l0j1,
             } else {
                 r2t[(d() + (d() >= la ? 1u : 0u)) * CP] = v;
             }
-        });
+        };
+        if constexpr (TAB) leaf_block_emit<S, true>(ME, seed, gw, sr, diag, Fm, emit, &tab);
+        else leaf_block_emit<S, true>(ME, seed, gw, sr, diag, Fm, emit);
         if constexpr (!BA_OM3W_LAB_NO_R2T) r2t[la * CP] = par;
         else asm volatile("" ::"v"(par));
     }
@@ -1010,6 +1084,101 @@ __global__ __launch_bounds__(kWaveThreads, BA_OM3W_MIN_BLOCKS(N)) void k_om3w(
         g_fused_stamps[blockIdx.x * wpb + wv][7] = __builtin_amdgcn_s_memrealtime();
     }
 #endif
+}
+
+// ---------------------------------------------------------------------------
+// k_om3wt: k_om3w with the pair-only half of the leaf calls' Philox rounds 0-1
+// shared across the wave through a pair table in LDS (Om3PairTable; DESIGN.md
+// §4).  Same task loop, inputs, level 0, rounds, roots, epilogue and fold; the
+// per-wave LDS image is k_om3w's followed by the table.  The table holds the
+// launch's upper word half gw_hi, so the launch must not straddle a multiple of
+// 2^32 trial words (launch_wave_engine checks and falls back to k_om3w).
+// Instantiated for n = 10 (the bench's tree); the 4 calls of the diagonal /
+// level-1 group stay as in k_om3w.
+// ---------------------------------------------------------------------------
+template <int N>
+struct Om3WT : Om3W<N> {
+    using T = Om3PairTable<N>;
+    static constexpr int oT = Om3W<N>::words;  // 16-byte aligned: words is even
+    static constexpr int words = oT + T::words;
+    // three blocks per CU (3 waves per SIMD, BA_OM3W_MIN_BLOCKS): their images and
+    // wave_flush_folded's 16 counters per wave, each block's sum rounded up to the
+    // LDS allocation granule (320 dwords on gfx950), must fit the CU's 160 KiB.
+    // A table 256 B per wave larger passed the occupancy query and the byte sum
+    // but ran two blocks per CU: the bench with two steps in flight lost 6%.
+    static constexpr int lds_granule = 1280;
+    static constexpr int block_bytes = (kWaveThreads / 64) * (words * 8 + 16 * 8);
+    static_assert(3 * ((block_bytes + lds_granule - 1) / lds_granule * lds_granule) <= 160 * 1024,
+                  "k_om3wt: three blocks' LDS per CU");
+};
+
+template <int N, bool STAGED = false>
+__global__ __launch_bounds__(kWaveThreads, BA_OM3W_MIN_BLOCKS(N)) void k_om3wt(
+    uint64_t seed, GenSpec gs, uint64_t first_trial, uint64_t batch,
+    const uint32_t* __restrict__ faulty, const uint8_t* __restrict__ order,
+    uint64_t* __restrict__ decisions, uint8_t* __restrict__ outcome,
+    uint64_t* __restrict__ counters, Sink sk) {
+    using G = Om3WT<N>;
+    constexpr int L = G::L, C = G::C, W = G::W, NIN = G::NIN;
+    constexpr uint32_t ME = 3;
+    extern __shared__ __attribute__((aligned(16))) uint64_t lds[];
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) >> 6,
+                   wpb = blockDim.x >> 6;
+    uint64_t* img = lds + (uint64_t)wv * G::words;
+    const uint64_t total_words = (batch + 63) / 64;
+    const uint64_t ntasks = (total_words + W - 1) / W;
+    uint64_t folded = 0;  // run counters folded per task (wave_fold_packed)
+    for (uint64_t task = (uint64_t)blockIdx.x * wpb + wv; task < ntasks;
+         task += (uint64_t)gridDim.x * wpb) {
+        // lane-derived values per task, as in k_om3w
+        uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+v"(lane));
+        const uint32_t lw_ = lane / C, la = lane - lw_ * C;
+        const bool act = lane < (uint32_t)G::LANES;
+        const uint32_t lw = act ? lw_ : 0;
+        const Om3LaneOffsets<N> lofs(la);
+        const uint64_t w0 = task * W;
+        const uint64_t gw0 = (first_trial >> 6) + w0;
+        if constexpr (STAGED)
+            stage_words<N, W>(img + G::oIN, lane, w0, batch, faulty, order);
+        else
+            wave_inputs<N, W, 0>(img + G::oIN, lane, w0, seed, gs, first_trial, batch, faulty, order);
+        __builtin_amdgcn_wave_barrier();
+        level0_r1t<N, W, G::LP>(img + G::oIN, img + G::oL0, img + G::oR1, lane, seed, gw0);
+        const uint64_t* in = img + G::oIN + lw * NIN;
+        uint64_t* erow = img + G::oE + lw * (C + 1);
+        if (act) erow[la] = in[la + 2];
+        __builtin_amdgcn_wave_barrier();
+        const uint64_t gw = gw0 + lw;
+        // the lane's side of the pair table: its block's row, its builder step, and
+        // the per-(word, level) constants of its own word at the leaf level
+        Om3PairTable<N> tab;
+        tab.row = (char*)(img + G::oT) + la * (uint32_t)Om3PairTable<N>::ROW;
+        tab.bw = lw < (uint32_t)Om3PairTable<N>::S ? lw : (uint32_t)Om3PairTable<N>::S - 1;
+        tab.pair0 = 0;
+        tab.gw_hi = (uint32_t)((first_trial >> 6) >> 32);
+        tab.k1 = (uint32_t)(seed >> 32);
+        tab.wc = philox_word_consts(ME, (uint32_t)gw, (uint32_t)seed, (uint32_t)(seed >> 32));
+        for (uint32_t j1 = 0; j1 < (uint32_t)L; ++j1) {
+            wave_alternate_priority(j1);
+            const uint64_t r1 = om3_round<N, true>(in, act ? img[G::oL0 + lw * L + j1] : 0ull,
+                                                   img + G::oR2, lw, la, act, j1, seed, gw,
+                                                   erow, &lofs, (const Om3PairTable<N>*)&tab);
+            if (act) img[G::oR1 + (lw * L + la + (la >= j1 ? 1u : 0u)) * G::LP + j1] = r1;
+        }
+        __builtin_amdgcn_wave_barrier();
+        roots_r1t<L, W, G::LP>(img + G::oR1, img + G::oAU, lane);
+        __builtin_amdgcn_wave_barrier();
+        {
+            TrialCounts tc;
+            wave_epilogue<N, W, ME, 0>(img + G::oIN, img + G::oAU, lane, w0, batch, decisions,
+                                       outcome, tc);
+            wave_fold_packed<N, W>(tc, lane, img + G::oL0, folded);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    wave_flush_folded(folded, __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), wv,
+                      wpb, counters, sk, false);
 }
 
 // ---------------------------------------------------------------------------

@@ -16,9 +16,26 @@ bool wave_supported(const Geometry& g) {
     return (g.me == 3 && g.n >= 5 && g.n <= 14) || (g.me == 4 && g.n >= 6 && g.n <= kWave4MaxN);
 }
 
+hipError_t launch_wave3t(const RunArgs& a);                   // ba_wave3t.hip (n = 10)
+
+// k_om3wt's pair table holds ONE upper half of the global trial-word index: the
+// launch may use it when every word its tasks touch (the last task padded to a
+// whole one) shares that half.  BA_OM3W_TABLE=0 (read per call: tests and A/B
+// runs switch it in-process) keeps k_om3w.
+template <int W>
+static bool pair_table_applies(const RunArgs& a) {
+    if (const char* e = getenv("BA_OM3W_TABLE"))
+        if (atoi(e) == 0) return false;
+    const uint64_t words = (a.batch + 63) / 64, tasks = (words + W - 1) / W;
+    if (tasks == 0) return false;
+    const uint64_t first = a.first_trial >> 6, last = first + tasks * W - 1;
+    return last >= first && (first >> 32) == (last >> 32);
+}
+
 hipError_t launch_wave_engine(const RunArgs& a, const Geometry& g) {
     if (g.me == 4) return launch_wave4(a, g);
     if (g.me != 3) return hipErrorInvalidValue;
+    if (g.n == 10 && pair_table_applies<Om3W<10>::W>(a)) return launch_wave3t(a);
     // depth 3: k_om3w (the rejected alternatives live in tools/lab_kernels.hpp)
     switch (g.n) {
 #define OM3W_CASE(nn) \

@@ -8,6 +8,15 @@ counter (profiles/*pmc_wave*.json) and the lab variants that pad one group each
 (BA_OM3W_R2T_PAD, BA_OM3W_R1T_PAD, BA_OM3W_E_PAD; tools/gpu_session.sh `bank`).
 
     python tools/lds_bank_model.py [--n 10] [--r2t-pad 1] [--r1t-pad 0] [--e-pad 1] [--waves 2048]
+                                   [--table [--table-row BYTES]]
+
+--table adds k_om3wt's pair table (Om3PairTable: two chunk slots of C rows of
+--table-row bytes, S 8-byte {hi, lo} words then S w1 dwords per row): per round
+three build passes (every lane (w, la) writes entry min(w, S - 1) of row la: ds_write_b64 +
+ds_write_b32) and 21 entry reads (lane (w, la) reads entry s of row la: 8
+distinct addresses, each broadcast to 8 lanes; the ISA has them as ds_read_b64 /
+ds_read2_b64 and ds_read_b32 / ds_read2_b32, both forms are modelled and the
+worse one counted).
 
 Instruction shapes, from the kernel's ISA (hipcc -S of ba_wave3.hip): the
 per-round input/E reads and the E update are ds_read_b64 / ds_write_b64, the R2T
@@ -25,11 +34,13 @@ GROUPS = {
     "ds_read_b64": ([list(range(0, 32)), list(range(32, 64))], lambda a: (a // 4) % 64),
     "ds_write_b64": ([list(range(16 * g, 16 * g + 16)) for g in range(4)], lambda a: (a // 4) % 32),
     "ds_read2_b64": ([list(range(16 * g, 16 * g + 16)) for g in range(4)], lambda a: (a // 4) % 32),
+    "ds_read_b32": ([list(range(0, 32)), list(range(32, 64))], lambda a: (a // 4) % 32),  # also each half of ds_read2_b32
+    "ds_write_b32": ([list(range(0, 32)), list(range(32, 64))], lambda a: (a // 4) % 32),
 }
 
 
-def extra_cycles(instr, addrs):
-    """addrs: {lane: byte address of an 8-byte access} for the active lanes."""
+def extra_cycles(instr, addrs, size=8):
+    """addrs: {lane: byte address of a `size`-byte access} for the active lanes."""
     groups, bank = GROUPS[instr]
     extra = 0
     for g in groups:
@@ -37,14 +48,37 @@ def extra_cycles(instr, addrs):
         for lane in g:
             if lane in addrs:
                 a = addrs[lane]
-                for dw in (a, a + 4):  # 8 bytes = two dwords
+                for dw in range(a, a + size, 4):
                     per_bank[bank(dw)].add(dw)
         if per_bank:
             extra += max(len(v) for v in per_bank.values()) - 1
     return extra
 
 
-def model(n, r2t_pad=1, r1t_pad=0, e_pad=1):
+def table_model(n, row_bytes, base_words):
+    """k_om3wt's pair table, per wave task: {group: extra cycles}."""
+    L, S, C = n - 1, n - 3, n - 2
+    W = 64 // C
+    lanes = [(l, l // C, l % C) for l in range(W * C)]
+    slot = C * row_bytes
+    acc = collections.Counter()
+    for _ in range(L):
+        for k in range((S - 1) // 2):  # build passes: chunk k into slot k & 1
+            b = 8 * base_words + (k & 1) * slot
+            acc["table_build"] += extra_cycles("ds_write_b64", {l: b + la * row_bytes + 8 * min(lw, S - 1)
+                                                                for l, lw, la in lanes})
+            acc["table_build"] += extra_cycles("ds_write_b32", {l: b + la * row_bytes + 8 * S + 4 * min(lw, S - 1)
+                                                                for l, lw, la in lanes}, 4)
+        for t in range(S * (S - 1) // 2):  # entry reads
+            b = 8 * base_words + ((t // S) & 1) * slot
+            a64 = {l: b + la * row_bytes + 8 * (t % S) for l, lw, la in lanes}
+            a32 = {l: b + la * row_bytes + 8 * S + 4 * (t % S) for l, lw, la in lanes}
+            acc["table_reads"] += max(extra_cycles("ds_read_b64", a64), extra_cycles("ds_read2_b64", a64))
+            acc["table_reads"] += extra_cycles("ds_read_b32", a32, 4)
+    return dict(acc)
+
+
+def model(n, r2t_pad=1, r1t_pad=0, e_pad=1, table_row=0):
     L, S, C = n - 1, n - 3, n - 2
     W = 64 // C
     NIN = n + 3
@@ -93,6 +127,8 @@ def model(n, r2t_pad=1, r1t_pad=0, e_pad=1):
                 if j + h < L:
                     acc["r1t_roots"] += extra_cycles("ds_read2_b64", {l: 8 * (oR1 + it * LP + j + h)
                                                                       for l, it in its.items()})
+    if table_row:  # the table follows k_om3w's image: after E[W][C + 1] (e_pad = 1), even words
+        acc.update(table_model(n, table_row, (oE + W * EP + 1) & ~1))
     return dict(acc)
 
 
@@ -103,10 +139,13 @@ def main():
     ap.add_argument("--r1t-pad", type=int, default=0)
     ap.add_argument("--e-pad", type=int, default=1)
     ap.add_argument("--waves", type=int, default=2048, help="wave tasks per launch (1M trials: 2048)")
+    ap.add_argument("--table", action="store_true", help="add k_om3wt's pair table")
+    ap.add_argument("--table-row", type=int, default=0, help="row bytes (default 12 S rounded up to 8)")
     a = ap.parse_args()
-    m = model(a.n, a.r2t_pad, a.r1t_pad, a.e_pad)
+    row = (a.table_row or (12 * (a.n - 3) + 7) // 8 * 8) if a.table else 0
+    m = model(a.n, a.r2t_pad, a.r1t_pad, a.e_pad, row)
     per_wave = sum(m.values())
-    print(json.dumps({"n": a.n, "r2t_pad": a.r2t_pad, "r1t_pad": a.r1t_pad, "e_pad": a.e_pad,
+    print(json.dumps({"n": a.n, "r2t_pad": a.r2t_pad, "r1t_pad": a.r1t_pad, "e_pad": a.e_pad, "table_row": row,
                       "extra_cycles_per_wave_task": m, "per_wave_task": per_wave,
                       "per_launch": per_wave * a.waves}))
 
