@@ -44,7 +44,7 @@ EXPORTS = ["ba_version", "ba_device_count", "ba_ctx_create", "ba_ctx_destroy", "
            "ba_split_share", "ba_split_votes_device", "ba_root_from_split_votes_device",
            "ba_comm_allgather_split_votes_device", "ba_run_instance_split_level_multi",
            "ba_clock_probe_device", "ba_ctx_memory", "ba_comm_set_timeout", "ba_comm_abort",
-           "ba_mt_table_device"]
+           "ba_mt_table_device", "ba_sm_run_trials", "ba_sm_run_trials_device", "ba_sm_coin_calls"]
 PROBE_BLOCKS = 2048  # BA_PROBE_BLOCKS
 
 
@@ -164,6 +164,12 @@ def load(path: str | None = None):
     lib.ba_comm_allgather_split_votes_device.argtypes = [vp, u32, u32, u32, u64, vp, vp]
     lib.ba_run_instance_split_level_multi.argtypes = [vp, vp, ctypes.POINTER(Params), u32, u64,
                                                       vp, vp, vp, vp, ctypes.POINTER(Counters)]
+    lib.ba_sm_run_trials.argtypes = [vp, ctypes.POINTER(Params), u64, vp, vp, vp, vp, vp,
+                                     ctypes.POINTER(Counters)]
+    lib.ba_sm_run_trials_device.argtypes = [vp, ctypes.POINTER(Params), u64, vp, vp, vp, vp, vp,
+                                            vp, vp]
+    lib.ba_sm_coin_calls.argtypes = [u32, u32]
+    lib.ba_sm_coin_calls.restype = u64
     if lib.ba_version() != ABI_VERSION:
         raise RuntimeError(f"libba_hip ABI {lib.ba_version()} != {ABI_VERSION}")
     if path is None:
@@ -214,6 +220,7 @@ class RunResult:
     decisions: np.ndarray | None
     outcome: np.ndarray | None
     counters: dict = field(default_factory=dict)
+    vsets: np.ndarray | None = None  # run_sm(want_vsets=True): bits 2(r-1) attack, 2(r-1)+1 retreat in V_r
 
     def decision(self, t: int, r: int) -> int:
         """Decision code of lieutenant r (1..n-1) in trial t."""
@@ -277,6 +284,33 @@ class Engine:
                                                 _ptr(order), _ptr(table), _ptr(poll), _ptr(dec),
                                                 _ptr(out), ctypes.byref(cnt)))
         return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])))
+
+    def run_sm(self, n, m, batch, seed=0, lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN, f=0,
+               order_mode=ORDER_GIVEN, order_value=ATTACK, first_trial=0, faulty=None, order=None,
+               want_decisions=True, want_outcome=True, want_vsets=False) -> RunResult:
+        """Resolve `batch` SM(m) signed-messages trials (docs/SEMANTICS.md §6) through
+        host buffers; the same inputs as `run` with equal keywords."""
+        faulty = None if faulty is None else np.ascontiguousarray(faulty, dtype=np.uint32)
+        order = None if order is None else np.ascontiguousarray(order, dtype=np.uint8)
+        dec = np.zeros(batch, np.uint64) if want_decisions else None
+        out = np.zeros(batch, np.uint8) if want_outcome else None
+        vs = np.zeros(batch, np.uint64) if want_vsets else None
+        p = make_params(n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, ENGINE_AUTO,
+                        first_trial)
+        cnt = Counters()
+        _check(self.lib, self.lib.ba_sm_run_trials(self.handle, ctypes.byref(p), batch, _ptr(faulty),
+                                                   _ptr(order), _ptr(dec), _ptr(out), _ptr(vs),
+                                                   ctypes.byref(cnt)))
+        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])), vs)
+
+    def run_sm_device(self, params: Params, batch: int, d_faulty=0, d_order=0, d_decisions=0,
+                      d_outcome=0, d_vsets=0, d_counters=0, stream=0):
+        """Enqueue SM(m) trials on device pointers (ba_sm_run_trials_device); asynchronous,
+        counters accumulated."""
+        _check(self.lib, self.lib.ba_sm_run_trials_device(
+            self.handle, ctypes.byref(params), batch, d_faulty or None, d_order or None,
+            d_decisions or None, d_outcome or None, d_vsets or None, d_counters or None,
+            stream or None))
 
     def stream(self) -> int:
         """The ctx's own HIP stream (ba_ctx_stream), as an int handle."""
@@ -529,6 +563,11 @@ def mt_table(n, m, seeds, faulty, poll=None, threads=0):
     _check(lib, lib.ba_mt_table(n, m, len(seeds), seeds.ctypes.data, faulty.ctypes.data,
                                 _ptr(poll), stride, tab.ctypes.data, nxt.ctypes.data, threads))
     return tab, nxt
+
+
+def sm_coin_calls(n: int, m: int) -> int:
+    """Philox calls SM(m) makes per 64-trial word: L + me L (L - 1) (ba_sm_coin_calls)."""
+    return int(load().ba_sm_coin_calls(n, m))
 
 
 def vote_slots(n: int, m: int, j_begin: int, j_end: int) -> int:

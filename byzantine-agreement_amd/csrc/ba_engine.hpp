@@ -191,4 +191,8 @@ hipError_t launch_levels_chunk(const RunArgs& a, const Geometry& g, const uint8_
 hipError_t launch_reduce(const uint64_t* partials, int rows, uint64_t* counters, hipStream_t s,
                          Prof* prof);
 
+// SM(m), signed messages (ba_sm.hip, docs/SEMANTICS.md §6): one wave per 64-trial
+// word; a.m is the in-bound parameter, a.me the relay rounds.  vsets optional.
+hipError_t launch_sm(const RunArgs& a, uint64_t* vsets);
+
 }  // namespace ba

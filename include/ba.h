@@ -218,6 +218,48 @@ int ba_run_trials_device(struct ba_ctx* ctx, const ba_params* p, uint64_t batch,
 int ba_gen_inputs_device(struct ba_ctx* ctx, const ba_params* p, uint64_t batch,
                          uint32_t* d_faulty_mask, uint8_t* d_order, void* stream);
 
+/* ---- SM(m): signed messages ------------------------------------------------
+ * Lamport, Shostak and Pease's other algorithm (no ba.py analogue: ba.py's
+ * messages are oral).  Signatures cannot be forged, so SM(m) copes with any
+ * f <= m traitors for any n, where OM(m) needs n > 3m.  One call resolves `batch`
+ * independent trials in the synchronous-round form of docs/SEMANTICS.md §6:
+ *   round 0      the commander signs and sends its order; a faulty commander
+ *                signs either value, each by a coin per lieutenant (§6 "Round 0");
+ *   accept       a lieutenant adds a received value it does not hold to its set
+ *                V, and the value is fresh for it next round (§6 "Accept");
+ *   rounds 1..me every lieutenant relays its fresh values with its signature
+ *                added, a loyal one to all, a faulty one by a coin per recipient
+ *                (§6 "Round k"); me = min(m, n-2);
+ *   decision     choice(V): V = {attack} -> attack, anything else -> retreat
+ *                (§6 "Decision"), then ba.py's quorum and the IC1/IC2 flags
+ *                (§6 "Epilogue"), with in-bound meaning |F| <= m.
+ * Coins are coin(64 + k, x) of the OM lie stream (§6 "Coins"); the synthetic
+ * inputs are ba_run_trials' own (§6 "Synthetic inputs"), so an OM and an SM run
+ * with equal params see the same faulty sets and orders.  decisions / outcome /
+ * counters: the layouts above; BA_C_UNDEF_DECISIONS is always 0 and
+ * BA_C_IN_BOUND / BA_C_BOUND_VIOL follow the SM bound.
+ */
+
+/* Lamport's SM(m) (signed messages); docs/SEMANTICS.md §6.  p->lie_mode must be
+ * BA_LIE_PHILOX (TABLE: BA_ENOTSUP), p->engine BA_ENGINE_AUTO (else BA_EINVAL);
+ * every faulty/order mode, first_trial and seed as in ba_run_trials.
+ * vsets[t] (optional): bit 2(r-1) = attack in V_r, bit 2(r-1)+1 = retreat in V_r.
+ * Both bits set is lieutenant r's proof that the commander signed two orders. */
+int ba_sm_run_trials(struct ba_ctx* ctx, const ba_params* p, uint64_t batch,
+                     const uint32_t* faulty_mask, const uint8_t* order,
+                     uint64_t* decisions, uint8_t* outcome, uint64_t* vsets,
+                     ba_counters* counters);              /* counters overwritten */
+/* The same rounds (§6 "Round 0" .. "Epilogue") on device buffers, enqueued on
+ * `stream` in the ctx's call order (NULL = HIP's null stream). */
+int ba_sm_run_trials_device(struct ba_ctx* ctx, const ba_params* p, uint64_t batch,
+                            const uint32_t* d_faulty_mask, const uint8_t* d_order,
+                            uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_vsets,
+                            uint64_t* d_counters, void* stream);  /* accumulated, async */
+/* §6 "Coins": L + me L (L-1), L = n-1 -- one call per lieutenant in round 0 and
+ * one per (sender, recipient) pair in each relay round (0 for n outside 1..32
+ * or m > 8). */
+uint64_t ba_sm_coin_calls(uint32_t n, uint32_t m);   /* Philox calls per 64-trial word; host only */
+
 /* ---- one huge instance split by first-hop subtree --------
  * The subtree of first-hop lieutenant j (relay paths starting 0 -> j) needs
  * only L_0[j]; its relay levels and inner majorities are independent of the
