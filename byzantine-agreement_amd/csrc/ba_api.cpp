@@ -493,6 +493,11 @@ static int validate(const ba_params* p, uint64_t batch, bool has_faulty, bool ha
         return fail(BA_EINVAL, "exact f=%u > n=%u", p->f, p->n);
     if (p->engine > BA_ENGINE_LEVELS) return fail(BA_EINVAL, "engine=%u", p->engine);
     if (p->first_trial & 63) return fail(BA_EINVAL, "first_trial must be a multiple of 64");
+    // the last trial's global index is first_trial + batch - 1 <= 2^64 - 1: a run
+    // may end exactly at 2^64, never wrap (every coin is keyed by that index)
+    if (batch > 0 && batch - 1 > UINT64_MAX - p->first_trial)
+        return fail(BA_EINVAL, "first_trial=%llu + batch=%llu reaches past trial index 2^64 - 1",
+                    (unsigned long long)p->first_trial, (unsigned long long)batch);
     if (batch && p->faulty_mode == BA_FAULTY_GIVEN && !has_faulty)
         return fail(BA_EINVAL, "BA_FAULTY_GIVEN needs faulty_mask");
     if (batch && p->order_mode == BA_ORDER_GIVEN && !has_order)

@@ -817,8 +817,9 @@ hipError_t launch_levels_chunk(const RunArgs& a, const Geometry& g, const uint8_
     // levels 0..kf in one k_relay_top launch; a materialised leaf level (no
     // leaf fusion) stays a k_relay launch, since a chain walk per leaf pair
     // would multiply the biggest level's draws.  BA_NO_TOP_RELAY=1: one
-    // k_relay launch per level (A/B and parity tests).
-    static const bool no_top = getenv("BA_NO_TOP_RELAY") && atoi(getenv("BA_NO_TOP_RELAY")) != 0;
+    // k_relay launch per level (A/B and parity tests; read per call, like the
+    // other fusion switches, so that tests switch it in-process).
+    const bool no_top = getenv("BA_NO_TOP_RELAY") && atoi(getenv("BA_NO_TOP_RELAY")) != 0;
     const uint32_t kf = (lay.leaf_fused || !job.tree || g.me == 0) ? ktop : g.me - 1;
     uint32_t k_first = 0;
     if (tin.fuse && (no_top || kf > (uint32_t)kTopMax)) {  // no k_relay_top: inputs on their own

@@ -102,7 +102,10 @@ typedef struct ba_params {
     uint32_t order_mode;   /* BA_ORDER_*                                          */
     uint32_t order_value;  /* BA_ORDER_CONST: BA_RETREAT/BA_ATTACK/BA_OTHER       */
     uint32_t engine;       /* BA_ENGINE_*                                         */
-    uint64_t first_trial;  /* global index of trial 0; multiple of 64             */
+    uint64_t first_trial;  /* global index of trial 0; multiple of 64.  The last
+                              trial, first_trial + batch - 1, may not pass
+                              2^64 - 1 (BA_EINVAL, every entry point): a run may
+                              end exactly at 2^64, never wrap                    */
     uint32_t table_stride; /* BA_LIE_TABLE: uint32 words per trial in lie_table   */
     uint32_t reserved[5];
 } ba_params;

@@ -26,9 +26,11 @@ ROOT = os.path.dirname(HERE)
 FAKE_RCCL = os.path.join(HERE, "native", "_build", "libfake_rccl.so")
 
 # (n, m, total trials, f, first_trial) of the trial-DP cases: ragged totals,
-# more ranks than words (70 trials = 2 words), every engine family
+# more ranks than words (70 trials = 2 words), every engine family; six words from
+# two below trial 2^38, where the lie stream's counter word carries (with three
+# ranks, rank 1's first_trial + share start is exactly 2^38)
 DP_CASES = [(10, 3, 64 * 37 + 11, 3, 0), (13, 4, 1000, 4, 64 * 3), (16, 5, 70, 5, 64 * 11),
-            (9, 2, 200, 3, 64)]
+            (9, 2, 200, 3, 64), (10, 3, 64 * 6, 5, 2**38 - 64 * 2)]
 # (n, m, level, batch, f, first_trial) of the split cases
 SPLIT_CASES = [(16, 5, 1, 1, 5, 64 * 7), (16, 5, 1, 70, 5, 64 * 7), (16, 5, 2, 1, 5, 64 * 7),
                (16, 5, 2, 70, 5, 64 * 7), (10, 3, 1, 130, 4, 0), (10, 3, 2, 130, 4, 0),
@@ -131,6 +133,9 @@ def main():
                 _, count = L.trial_share(total, world, rank)
                 dec = torch.zeros(max(count, 1), dtype=torch.int64, device=dev)
                 outc = torch.zeros(max(count, 1), dtype=torch.uint8, device=dev)
+                # the job runs on the communicator's own stream: torch's zero fills
+                # (its stream) must have landed before a kernel there writes results
+                torch.cuda.synchronize()
                 cnt, sf, sc = comm.run_trials(p, total, d_decisions=dec.data_ptr(),
                                               d_outcome=outc.data_ptr())
                 torch.cuda.synchronize()

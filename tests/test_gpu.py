@@ -220,6 +220,23 @@ def test_errors(engine):
     assert ei.value.code == L.EINVAL
     res = engine.run(5, 1, 0, faulty=[], order=[])
     assert res.counters["trials"] == 0
+    # the trial index is 64-bit and may not wrap: the last trial is at most 2^64 - 1
+    kw = dict(seed=3, faulty_mode=L.FAULTY_RANDOM, f=2, order_mode=L.ORDER_RANDOM,
+              first_trial=2**64 - 64)
+    with pytest.raises(L.BAError) as ei:
+        engine.run(5, 1, 65, **kw)
+    assert ei.value.code == L.EINVAL and "first_trial" in str(ei.value)
+    import torch
+    buf = torch.zeros(65, dtype=torch.int32, device="cuda")
+    with pytest.raises(L.BAError) as ei:
+        engine.gen_inputs_device(L.make_params(5, 1, **kw), 65, d_faulty=buf.data_ptr())
+    assert ei.value.code == L.EINVAL and "first_trial" in str(ei.value)
+    res = engine.run(5, 1, 64, **kw)  # ends exactly at 2^64: valid
+    od, oo, ocnt = oracle_c.run(5, 1, 64, **kw)
+    same(res.decisions, od, "decisions")
+    same(res.outcome, oo, "outcome")
+    assert {k: res.counters[k] for k in ocnt} == ocnt
+    assert engine.run(5, 1, 4, faulty=[1] * 4, order=[1] * 4).counters["trials"] == 4  # the ctx works on
 
 
 @pytest.mark.parametrize("n,m", [(10, 3), (7, 2), (13, 4), (9, 4), (16, 3)])

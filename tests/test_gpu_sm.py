@@ -223,6 +223,13 @@ def test_errors(engine):
         rc = engine.lib.ba_sm_run_trials(engine.handle, ctypes.byref(p), 64, None, None, None, None,
                                          None, ctypes.byref(cnt))
         assert rc == L.EINVAL and b"engine" in engine.lib.ba_last_error()
+    # the trial index may not wrap: the last trial is at most 2^64 - 1
+    with pytest.raises(L.BAError) as e:
+        engine.run_sm(4, 1, 65, first_trial=2**64 - 64, **kw)
+    assert e.value.code == L.EINVAL and "first_trial" in str(e.value)
+    top = engine.run_sm(4, 1, 64, first_trial=2**64 - 64, want_vsets=True, **kw)  # ends at 2^64: valid
+    dec, out, vs, cnt = S.run(4, 1, first_trial=2**64 - 64, batch=64, **kw)
+    check(top, (np.array(dec, np.uint64), np.array(out, np.uint8), np.array(vs, np.uint64), cnt), "top")
     # batch = 0: BA_OK with zero counters
     res = engine.run_sm(4, 1, 0, **kw)
     assert all(v == 0 for v in res.counters.values())

@@ -126,6 +126,92 @@ def test_c_gen_matches_python():
                     assert bin(pm).count("1") == min(n, f)
 
 
+# --- the 64-bit trial index (docs/SEMANTICS.md §3-§4) ---------------------------
+# Lie stream: ctr words 2, 3 = lo, hi of w = t // 64 (hi != 0 from t = 2^38 on).
+# Input stream: ctr words 2, 3 = lo, hi of t (hi != 0 from t = 2^32 on).  The Python
+# oracle computes with unbounded ints, the C code with uint64_t and casts.
+BIG_T = [2**32 - 1, 2**32, 2**38 - 1, 2**38, 2**38 + 65, 2**63, 2**64 - 1]
+BOUNDARY_STARTS = [2**32 - 64, 2**38 - 64]  # 192 trials: one word below, two above
+BOUNDARY_SHAPES = [(4, 1), (7, 2), (10, 3)]
+
+
+def test_lie_c_matches_python_above_2_32():
+    lib = oracle_c.load()
+    for t in BIG_T:
+        for seed in (0xBA5EED, 0x5157ED0123456789):
+            for k in (0, 1, 3, 7, 64 + 2):
+                for x in (0, 1, 2, 3, 71, 72, 503, 2**31 - 1):
+                    assert lib.ba_oracle_lie(seed, t, k, x) == O.lie(seed, t, k, x), (t, seed, k, x)
+
+
+def test_lie_stream_reads_both_halves_of_the_word_index():
+    """w_hi and w_lo each reach the coins: the word of t = 2^38 differs from the
+    words of t = 0 (same w_lo) and of t = 2^38 + 64 (same w_hi) over 64 slots."""
+    def word(t):
+        return [O.lie(0xBA5EED, t, 1, x) for x in range(64)]
+    assert word(2**38) != word(0)
+    assert word(2**38) != word(2**38 + 64)
+    assert word(2**38 + 63) != word(2**38 + 64)
+    a = [O.gen(10, 77, 1, 5, 1, 0, t) for t in range(2**32, 2**32 + 64)]
+    assert a != [O.gen(10, 77, 1, 5, 1, 0, t) for t in range(64)]
+
+
+def test_c_gen_matches_python_above_2_32():
+    lib = oracle_c.load()
+    fm = np.zeros(1, np.uint32)
+    oc = np.zeros(1, np.uint8)
+    for n in (1, 4, 10, 16, 32):
+        for mode, f in ((1, n // 3), (1, n), (2, min(n, 5)), (2, n)):
+            for t in BIG_T:
+                lib.ba_oracle_gen(n, 0x5157ED0123456789, mode, f, 1, 0, t, fm.ctypes.data,
+                                  oc.ctypes.data)
+                assert (int(fm[0]), int(oc[0])) == O.gen(n, 0x5157ED0123456789, mode, f, 1, 0, t), (n, mode, f, t)
+
+
+@pytest.mark.parametrize("first", BOUNDARY_STARTS)
+@pytest.mark.parametrize("n,m", BOUNDARY_SHAPES)
+def test_runs_across_a_counter_word_boundary(n, m, first):
+    """192 trials whose index crosses 2^32 (the input stream's ctr word 2 carries)
+    or 2^38 (the lie stream's): the recursion in C, in Python, and the word-sliced
+    port give the same decisions, outcome bytes and counters."""
+    B = 192
+    kw = dict(seed=0xBA5EED + n, faulty_mode=1, f=(n - 1) // 3 + 2, order_mode=1, first_trial=first)
+    d1, o1, c1 = oracle_c.run(n, m, B, **kw)
+    d2, o2, c2 = O.run(n, m, batch=B, **kw)
+    d3, o3, c3 = oracle_c.sliced_run(n, m, B, **kw)
+    assert [int(x) for x in d1] == d2 and [int(x) for x in o1] == o2 and c1 == c2
+    assert np.array_equal(d1, d3) and np.array_equal(o1, o3) and c1 == c3
+    # the two sides of the boundary are different draws, not one word repeated
+    assert not np.array_equal(d1[:64], d1[64:128]) and not np.array_equal(d1[64:128], d1[128:])
+
+
+@pytest.mark.parametrize("first", BOUNDARY_STARTS + [2**64 - 192])
+def test_sliced_gen_across_a_counter_word_boundary(first):
+    lib = oracle_c.load()
+    a, b = np.zeros(1, np.uint32), np.zeros(1, np.uint8)
+    for n in (1, 4, 10, 32):
+        for mode, f in ((1, n), (2, (n + 1) // 2)):
+            fm, oc = oracle_c.sliced_gen(n, 192, seed=99, faulty_mode=mode, f=f, order_mode=1,
+                                         first_trial=first)
+            for i in range(192):
+                lib.ba_oracle_gen(n, 99, mode, f, 1, 1, first + i, a.ctypes.data, b.ctypes.data)
+                assert (int(fm[i]), int(oc[i])) == (int(a[0]), int(b[0])), (n, mode, f, first, i)
+
+
+@pytest.mark.parametrize("n,m", [(4, 1), (5, 2), (6, 3)])
+def test_levels_model_matches_oracle_across_2_38(n, m):
+    """The slot arithmetic's lie words at the three trial words of first_trial =
+    2^38 - 64: gw = 2^32 - 1 (hi 0), 2^32 and 2^32 + 1 (hi 1)."""
+    seed, first = 0xBA5EED, 2**38 - 64
+    for gw in range(first >> 6, (first >> 6) + 3):
+        ins = [O.gen(n, seed, 1, (n - 1) // 3 + 2, 1, 0, t) for t in range(64 * gw, 64 * gw + 64)]
+        fm, oc = [a for a, _ in ins], [b for _, b in ins]
+        dec = levels_model.run_word(n, m, seed, gw, fm, oc)
+        d2, _, _ = oracle_c.run(n, m, 64, seed=seed, faulty=fm, order=oc, first_trial=64 * gw)
+        for t in range(64):
+            assert dec[t] == [(int(d2[t]) >> (2 * r)) & 3 for r in range(n - 1)], (gw, t)
+
+
 # --- OM theory properties ------------------------------------------------------
 @pytest.mark.parametrize("n,m", [(4, 1), (7, 2), (10, 3), (13, 4)])
 def test_om_guarantee_within_bound(n, m):

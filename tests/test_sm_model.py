@@ -62,6 +62,18 @@ def test_plane_form_equals_chain_form_on_theorem_inputs(n, m):
     assert _theorem_run(n, m, "plane") == _theorem_run(n, m)
 
 
+@pytest.mark.parametrize("n,m", [(4, 1), (5, 2), (7, 3)])
+def test_plane_form_equals_chain_form_across_2_38(n, m):
+    """192 trials from first_trial = 2^38 - 64: the plane form keys its coin words
+    by the trial word (2^32 - 1, then 2^32 and 2^32 + 1 with the upper counter
+    word set), the chain form by the trial; every general may be faulty."""
+    kw = dict(seed=0x5157ED0123456789, faulty_mode=O.FAULTY_RANDOM, f=n, order_mode=O.ORDER_RANDOM,
+              first_trial=2**38 - 64, batch=192)
+    chain = S.run(n, m, form="chain", **kw)
+    assert S.run(n, m, form="plane", **kw) == chain
+    assert chain[3]["trials"] == 192 and chain[0][:64] != chain[0][64:128] != chain[0][128:]
+
+
 def test_decision_rule_and_vset_packing():
     # a loyal commander and no traitor: V = {order} everywhere, in both packings
     dec, out, vs, cnt = S.run(5, 2, seed=3, faulty=[0, 0, 0], order=[1, 0, 2], batch=3)
