@@ -4,6 +4,7 @@
 // Instantiated by ba_wave3.hip / ba_wave4.hip (two translation units, so the
 // two kernel families compile in parallel).
 #pragma once
+#include "ba_bitslice.hpp"
 #include "ba_leaf.hpp"
 
 namespace ba {
@@ -217,6 +218,27 @@ __device__ __forceinline__ void stage_words(uint64_t* in0, uint32_t lane, uint64
     static_for<0, W>([&](auto q) {
         stage_slice<N>(in0 + q() * NIN, lane, fm[q()], oc[q()], (w0 + q()) * 64 + lane < batch);
     });
+}
+
+// Byte-sliced staging (k_om3wt, W = 8): lane (w, k) = (lane >> 3, lane & 7) owns
+// the 8 trials of byte k of word w -- the wave's 64 lanes read the task's 512
+// faulty masks and order bytes as one contiguous run, 32 + 8 bytes per lane in
+// three wide loads -- and turns them into byte k of the word's N+3 planes with
+// two 8x8 bit transposes in registers (stage_pack, ba_bitslice.hpp), stored
+// into the same in0[w*(N+3) + g] image that stage_words fills.  Against the
+// ballots and writelanes of stage_slice: ~1/4 of the vector instructions, no
+// SGPR round trip and no wait states.  A lane not wholly inside the batch
+// loads trial by trial under a guard (stage_load).
+template <int N, int W>
+__device__ __forceinline__ void stage_words_sliced(uint64_t* in0, uint32_t lane, uint64_t w0,
+                                                   uint64_t batch,
+                                                   const uint32_t* __restrict__ faulty,
+                                                   const uint8_t* __restrict__ order) {
+    static_assert(W == 8, "lane = (word, byte): 8 words x 8 bytes");
+    constexpr int NIN = N + 3;
+    const StagePlanes<N> p = stage_pack<N>(stage_load(faulty, order, w0 * 64, 8 * lane, batch));
+    uint8_t* dst = reinterpret_cast<uint8_t*>(in0 + (lane >> 3) * NIN) + (lane & 7u);
+    static_for<0, NIN>([&](auto g) { dst[8 * g()] = (uint8_t)p.template plane<g()>(); });
 }
 
 // ---------------------------------------------------------------------------
@@ -457,6 +479,62 @@ __device__ __forceinline__ void wave_epilogue(uint64_t* in0, const uint64_t* au0
         if (live) {
             if (!(DIAG & 1) && decisions) decisions[i] = dec;
             if (!(DIAG & 2) && outcome) outcome[i] = (uint8_t)out;
+        }
+    }
+}
+
+// The quorum epilogue of k_om3wt (W = 8), both phases in the layout lane =
+// (word, byte): after epilogue_core the lane holds byte k of the six outcome
+// planes in registers and has read byte k of the root planes, i.e. everything
+// about its 8 trials, so it transposes them into the trials' decision words and
+// outcome bytes itself (pick_out, ba_bitslice.hpp) and stores them: 64
+// contiguous bytes of decisions and 8 of outcomes per lane, contiguous across
+// the wave.  The outcome planes make no LDS round trip and phase 2 of
+// wave_epilogue (lane = trial, one bfe + shift-or per output bit) is not run.
+// A lane whose live byte is not all ones stores trial by trial under the live
+// bit; nothing is stored at or beyond batch (the live plane is 0 there).
+template <int N, int W, uint32_t ME>
+__device__ __forceinline__ void wave_epilogue_sliced(const uint64_t* in0, const uint64_t* au0,
+                                                     uint32_t lane, uint64_t w0,
+                                                     uint64_t* __restrict__ decisions,
+                                                     uint8_t* __restrict__ outcome, TrialCounts& tc) {
+    static_assert(W == 8, "lane = (word, byte): 8 words x 8 bytes");
+    constexpr int L = N - 1, NIN = N + 3;
+    const uint8_t* ib = reinterpret_cast<const uint8_t*>(in0 + (lane >> 3) * NIN) + (lane & 7u);
+    const uint8_t* ab = reinterpret_cast<const uint8_t*>(au0 + (lane >> 3) * 2 * L) + (lane & 7u);
+    uint32_t a[L], u[L], o[6];
+    static_for<0, L>([&](auto b) {
+        a[b()] = ab[8 * b()];
+        u[b()] = L % 2 == 0 ? (uint32_t)ab[8 * (L + b())] : 0u;
+    });
+    epilogue_core<N, ME, uint32_t>([&](int p) -> uint32_t { return ib[8 * p]; },
+                                   [&](int b) -> uint32_t { return b < L ? a[b] : u[b - L]; },
+                                   [&](int k, uint32_t v) { o[k] = v; }, tc);
+    const uint32_t live = ib[8 * (N + 2)];
+    const PickOut<L> r = pick_out<L>(a, u, o);
+    const uint64_t i0 = w0 * 64 + 8 * lane;
+    if (live == 0xffu) {
+        if (decisions)
+            static_for<0, 4>([&](auto q) {
+                *reinterpret_cast<U64x2*>(decisions + i0 + 2 * q()) =
+                    U64x2{r.dec[2 * q()], r.dec[2 * q() + 1]};
+            });
+        if (outcome) *reinterpret_cast<U32x2*>(outcome + i0) = U32x2{r.out_lo, r.out_hi};
+    } else if (live != 0) {
+        // rare (the batch's last lanes): one small loop, the values shifted down
+        // so that no register is indexed
+        uint32_t dec[8], lv = live, olo = r.out_lo, ohi = r.out_hi;
+        static_for<0, 8>([&](auto t) { dec[t()] = r.dec[t()]; });
+#pragma clang loop unroll(disable)
+        for (uint32_t t = 0; t < 8; ++t) {
+            if (lv & 1u) {
+                if (decisions) decisions[i0 + t] = dec[0];
+                if (outcome) outcome[i0 + t] = (uint8_t)olo;
+            }
+            static_for<0, 7>([&](auto k) { dec[k()] = dec[k() + 1]; });
+            olo = olo >> 8 | ohi << 24;
+            ohi >>= 8;
+            lv >>= 1;
         }
     }
 }
@@ -1089,12 +1167,12 @@ __global__ __launch_bounds__(kWaveThreads, BA_OM3W_MIN_BLOCKS(N)) void k_om3w(
 // ---------------------------------------------------------------------------
 // k_om3wt: k_om3w with the pair-only half of the leaf calls' Philox rounds 0-1
 // shared across the wave through a pair table in LDS (Om3PairTable; DESIGN.md
-// §4).  Same task loop, inputs, level 0, rounds, roots, epilogue and fold; the
-// per-wave LDS image is k_om3w's followed by the table.  The table holds the
-// launch's upper word half gw_hi, so the launch must not straddle a multiple of
-// 2^32 trial words (launch_wave_engine checks and falls back to k_om3w).
-// Instantiated for n = 10 (the bench's tree); the 4 calls of the diagonal /
-// level-1 group stay as in k_om3w.
+// §4), staged inputs and results byte-sliced (stage_words_sliced,
+// wave_epilogue_sliced); the rest is k_om3w's, and the per-wave LDS image is
+// k_om3w's followed by the table.  The table holds the launch's upper word half
+// gw_hi, so the launch must not straddle a multiple of 2^32 trial words
+// (launch_wave_engine checks and falls back to k_om3w).  Instantiated for n = 10
+// (the bench's tree); the diagonal / level-1 group's 4 calls stay as in k_om3w.
 // ---------------------------------------------------------------------------
 template <int N>
 struct Om3WT : Om3W<N> {
@@ -1140,7 +1218,7 @@ __global__ __launch_bounds__(kWaveThreads, BA_OM3W_MIN_BLOCKS(N)) void k_om3wt(
         const uint64_t w0 = task * W;
         const uint64_t gw0 = (first_trial >> 6) + w0;
         if constexpr (STAGED)
-            stage_words<N, W>(img + G::oIN, lane, w0, batch, faulty, order);
+            stage_words_sliced<N, W>(img + G::oIN, lane, w0, batch, faulty, order);
         else
             wave_inputs<N, W, 0>(img + G::oIN, lane, w0, seed, gs, first_trial, batch, faulty, order);
         __builtin_amdgcn_wave_barrier();
@@ -1171,8 +1249,8 @@ __global__ __launch_bounds__(kWaveThreads, BA_OM3W_MIN_BLOCKS(N)) void k_om3wt(
         __builtin_amdgcn_wave_barrier();
         {
             TrialCounts tc;
-            wave_epilogue<N, W, ME, 0>(img + G::oIN, img + G::oAU, lane, w0, batch, decisions,
-                                       outcome, tc);
+            wave_epilogue_sliced<N, W, ME>(img + G::oIN, img + G::oAU, lane, w0, decisions, outcome,
+                                           tc);
             wave_fold_packed<N, W>(tc, lane, img + G::oL0, folded);
         }
         __builtin_amdgcn_wave_barrier();
