@@ -29,6 +29,7 @@ RETREAT, ATTACK, OTHER, UNDEFINED = 0, 1, 2, 2
 Q_RETREAT, Q_ATTACK, Q_UNDETERMINED = 0, 1, 2
 ENGINE_AUTO, ENGINE_FUSED, ENGINE_LEVELS = 0, 1, 2
 SPLIT_FIRST_HOP, SPLIT_SECOND_HOP = 1, 2
+ADV_SPLIT, ADV_FLIP, ADV_ANTI = 0, 1, 2  # scripted traitor policies (docs/SEMANTICS.md §7)
 COUNTER_NAMES = ["trials", "agreement", "validity_applicable", "validity", "quorum_retreat",
                  "quorum_attack", "quorum_undetermined", "undefined_decisions", "in_bound",
                  "bound_violations", "faulty_total", "attack_decisions"]
@@ -44,7 +45,8 @@ EXPORTS = ["ba_version", "ba_device_count", "ba_ctx_create", "ba_ctx_destroy", "
            "ba_split_share", "ba_split_votes_device", "ba_root_from_split_votes_device",
            "ba_comm_allgather_split_votes_device", "ba_run_instance_split_level_multi",
            "ba_clock_probe_device", "ba_ctx_memory", "ba_comm_set_timeout", "ba_comm_abort",
-           "ba_mt_table_device", "ba_sm_run_trials", "ba_sm_run_trials_device", "ba_sm_coin_calls"]
+           "ba_mt_table_device", "ba_sm_run_trials", "ba_sm_run_trials_device", "ba_sm_coin_calls",
+           "ba_adv_run_trials", "ba_adv_run_trials_device", "ba_adv_paths"]
 PROBE_BLOCKS = 2048  # BA_PROBE_BLOCKS
 
 
@@ -170,6 +172,12 @@ def load(path: str | None = None):
                                             vp, vp]
     lib.ba_sm_coin_calls.argtypes = [u32, u32]
     lib.ba_sm_coin_calls.restype = u64
+    lib.ba_adv_run_trials.argtypes = [vp, ctypes.POINTER(Params), u32, u64, vp, vp, vp, vp,
+                                      ctypes.POINTER(Counters)]
+    lib.ba_adv_run_trials_device.argtypes = [vp, ctypes.POINTER(Params), u32, u64, vp, vp, vp, vp,
+                                             vp, vp]
+    lib.ba_adv_paths.argtypes = [u32, u32]
+    lib.ba_adv_paths.restype = u64
     if lib.ba_version() != ABI_VERSION:
         raise RuntimeError(f"libba_hip ABI {lib.ba_version()} != {ABI_VERSION}")
     if path is None:
@@ -311,6 +319,32 @@ class Engine:
             self.handle, ctypes.byref(params), batch, d_faulty or None, d_order or None,
             d_decisions or None, d_outcome or None, d_vsets or None, d_counters or None,
             stream or None))
+
+    def run_adv(self, n, m, batch, policy, seed=0, lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN, f=0,
+                order_mode=ORDER_GIVEN, order_value=ATTACK, engine=ENGINE_AUTO, first_trial=0,
+                faulty=None, order=None, want_decisions=True, want_outcome=True) -> RunResult:
+        """Resolve `batch` OM(m) trials whose traitors follow a scripted policy (ADV_SPLIT,
+        ADV_FLIP, ADV_ANTI; docs/SEMANTICS.md §7) through host buffers; the same inputs as
+        `run` with equal keywords."""
+        faulty = None if faulty is None else np.ascontiguousarray(faulty, dtype=np.uint32)
+        order = None if order is None else np.ascontiguousarray(order, dtype=np.uint8)
+        dec = np.zeros(batch, np.uint64) if want_decisions else None
+        out = np.zeros(batch, np.uint8) if want_outcome else None
+        p = make_params(n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, engine,
+                        first_trial)
+        cnt = Counters()
+        _check(self.lib, self.lib.ba_adv_run_trials(self.handle, ctypes.byref(p), policy, batch,
+                                                    _ptr(faulty), _ptr(order), _ptr(dec), _ptr(out),
+                                                    ctypes.byref(cnt)))
+        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])))
+
+    def run_adv_device(self, params: Params, batch: int, policy: int, d_faulty=0, d_order=0,
+                       d_decisions=0, d_outcome=0, d_counters=0, stream=0):
+        """Enqueue scripted-policy trials on device pointers (ba_adv_run_trials_device);
+        asynchronous, counters accumulated."""
+        _check(self.lib, self.lib.ba_adv_run_trials_device(
+            self.handle, ctypes.byref(params), policy, batch, d_faulty or None, d_order or None,
+            d_decisions or None, d_outcome or None, d_counters or None, stream or None))
 
     def stream(self) -> int:
         """The ctx's own HIP stream (ba_ctx_stream), as an int handle."""
@@ -568,6 +602,11 @@ def mt_table(n, m, seeds, faulty, poll=None, threads=0):
 def sm_coin_calls(n: int, m: int) -> int:
     """Philox calls SM(m) makes per 64-trial word: L + me L (L - 1) (ba_sm_coin_calls)."""
     return int(load().ba_sm_coin_calls(n, m))
+
+
+def adv_paths(n: int, m: int) -> int:
+    """Relay chains one receiver walks under a scripted policy: P(n-2, me) (ba_adv_paths)."""
+    return int(load().ba_adv_paths(n, m))
 
 
 def vote_slots(n: int, m: int, j_begin: int, j_end: int) -> int:

@@ -195,4 +195,8 @@ hipError_t launch_reduce(const uint64_t* partials, int rows, uint64_t* counters,
 // word; a.m is the in-bound parameter, a.me the relay rounds.  vsets optional.
 hipError_t launch_sm(const RunArgs& a, uint64_t* vsets);
 
+// OM(m) under a scripted traitor policy (ba_adv.hip, docs/SEMANTICS.md §7): one
+// thread per (64-trial word, receiver), no lie draws.  policy: BA_ADV_*.
+hipError_t launch_adv(const RunArgs& a, uint32_t policy);
+
 }  // namespace ba

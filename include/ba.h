@@ -263,6 +263,44 @@ int ba_sm_run_trials_device(struct ba_ctx* ctx, const ba_params* p, uint64_t bat
  * or m > 8). */
 uint64_t ba_sm_coin_calls(uint32_t n, uint32_t m);   /* Philox calls per 64-trial word; host only */
 
+/* ---- OM(m) against scripted traitors ------------------------------------------
+ * ba_run_trials' traitors flip a fair coin per message; these entries replace
+ * the coin by a deterministic policy (docs/SEMANTICS.md §7), which is how
+ * Lamport, Shostak and Pease argue: with n <= 3m a traitor that chooses its
+ * messages breaks OM(m), with n > 3m no choice does.  Everything but the lie
+ * rule is ba_run_trials': effective depth, majorities, root tie -> undefined,
+ * quorum, flags, the in-bound rule and the synthetic inputs (an OM and an ADV
+ * run with equal params see the same faulty sets and orders).  A faulty sender
+ * (the commander at level 0, else the path's last lieutenant) shows recipient
+ * rank j, in place of the truth T it holds:
+ *   BA_ADV_SPLIT  attack to odd ranks, retreat to even ones, at every level
+ *                 (the paper's two-faced traitor);
+ *   BA_ADV_FLIP   1 - T;
+ *   BA_ADV_ANTI   level 0 as SPLIT; deeper, the opposite of what j itself got
+ *                 from the commander (aims at ties).
+ * No coin is drawn: results depend on (n, m, policy, faulty set, order) only, and
+ * on seed / first_trial only through the synthetic inputs.  p->lie_mode must be
+ * BA_LIE_PHILOX (TABLE: BA_ENOTSUP), p->engine BA_ENGINE_AUTO (else BA_EINVAL),
+ * policy <= BA_ADV_ANTI (else BA_EINVAL).  A receiver walks its ba_adv_paths(n, m)
+ * relay chains one by one; above 2^24 of them the call is BA_ETOOBIG ((16,6),
+ * (32,4), (12,8) fit; (32,5), (16,7), (16,8) do not).  decisions / outcome /
+ * counters: the OM layouts above. */
+#define BA_ADV_SPLIT 0
+#define BA_ADV_FLIP 1
+#define BA_ADV_ANTI 2
+int ba_adv_run_trials(struct ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
+                      const uint32_t* faulty_mask, const uint8_t* order, uint64_t* decisions,
+                      uint8_t* outcome, ba_counters* counters);  /* counters overwritten */
+/* The same walk on device buffers, enqueued on `stream` in the ctx's call order
+ * (NULL = HIP's null stream). */
+int ba_adv_run_trials_device(struct ba_ctx* ctx, const ba_params* p, uint32_t policy,
+                             uint64_t batch, const uint32_t* d_faulty_mask,
+                             const uint8_t* d_order, uint64_t* d_decisions, uint8_t* d_outcome,
+                             uint64_t* d_counters, void* stream);  /* accumulated, async */
+/* P(n-2, me): the leaf chains one receiver resolves (§7); 1 when me = 0, and 0 for
+ * n outside 1..32 or m > 8. */
+uint64_t ba_adv_paths(uint32_t n, uint32_t m);   /* host only */
+
 /* ---- one huge instance split by first-hop subtree --------
  * The subtree of first-hop lieutenant j (relay paths starting 0 -> j) needs
  * only L_0[j]; its relay levels and inner majorities are independent of the
