@@ -46,7 +46,10 @@ EXPORTS = ["ba_version", "ba_device_count", "ba_ctx_create", "ba_ctx_destroy", "
            "ba_comm_allgather_split_votes_device", "ba_run_instance_split_level_multi",
            "ba_clock_probe_device", "ba_ctx_memory", "ba_comm_set_timeout", "ba_comm_abort",
            "ba_mt_table_device", "ba_sm_run_trials", "ba_sm_run_trials_device", "ba_sm_coin_calls",
-           "ba_adv_run_trials", "ba_adv_run_trials_device", "ba_adv_paths"]
+           "ba_adv_run_trials", "ba_adv_run_trials_device", "ba_adv_paths",
+           "ba_enum_bits", "ba_enum_slots", "ba_enum_run", "ba_enum_run_device"]
+ENUM_MAX_BITS = 48  # BA_ENUM_MAX_BITS (docs/SEMANTICS.md §8)
+NO_WITNESS = (1 << 64) - 1
 PROBE_BLOCKS = 2048  # BA_PROBE_BLOCKS
 
 
@@ -178,6 +181,12 @@ def load(path: str | None = None):
                                              vp, vp]
     lib.ba_adv_paths.argtypes = [u32, u32]
     lib.ba_adv_paths.restype = u64
+    lib.ba_enum_bits.argtypes = [u32, u32, u32]
+    lib.ba_enum_bits.restype = u32
+    lib.ba_enum_slots.argtypes = [u32, u32, u32, vp, vp, u32]
+    lib.ba_enum_run.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u64, vp, vp,
+                                ctypes.POINTER(Counters), ctypes.POINTER(u64)]
+    lib.ba_enum_run_device.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u64, vp, vp, vp, vp, vp]
     if lib.ba_version() != ABI_VERSION:
         raise RuntimeError(f"libba_hip ABI {lib.ba_version()} != {ABI_VERSION}")
     if path is None:
@@ -229,6 +238,7 @@ class RunResult:
     outcome: np.ndarray | None
     counters: dict = field(default_factory=dict)
     vsets: np.ndarray | None = None  # run_sm(want_vsets=True): bits 2(r-1) attack, 2(r-1)+1 retreat in V_r
+    witness: int | None = None  # run_enum: the smallest violating strategy, None when there is none
 
     def decision(self, t: int, r: int) -> int:
         """Decision code of lieutenant r (1..n-1) in trial t."""
@@ -345,6 +355,38 @@ class Engine:
         _check(self.lib, self.lib.ba_adv_run_trials_device(
             self.handle, ctypes.byref(params), policy, batch, d_faulty or None, d_order or None,
             d_decisions or None, d_outcome or None, d_counters or None, stream or None))
+
+    def run_enum(self, n, m, faulty_mask, order, first=0, count=None, want_decisions=False,
+                 want_outcome=False, lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN,
+                 order_mode=ORDER_GIVEN, engine=ENGINE_AUTO) -> RunResult:
+        """Walk the traitor strategies S in [first, first + count) of the case (n, m,
+        faulty_mask, order) (docs/SEMANTICS.md §8; ba_enum_run); count=None: up to the end
+        of the space, 2^enum_bits.  The result's `witness` is the smallest violating S of
+        the range (decode_strategy reads it), None when no strategy violates."""
+        if count is None:
+            b = enum_bits(n, m, faulty_mask)
+            count = max(0, (1 << b) - first) if b <= ENUM_MAX_BITS else 0  # above the cap: the call says so
+        dec = np.zeros(count, np.uint64) if want_decisions else None
+        out = np.zeros(count, np.uint8) if want_outcome else None
+        p = make_params(n, m, 0, lie_mode, faulty_mode, 0, order_mode, ATTACK, engine, first)
+        cnt, wit = Counters(), ctypes.c_uint64(NO_WITNESS)
+        _check(self.lib, self.lib.ba_enum_run(self.handle, ctypes.byref(p), faulty_mask & 0xFFFFFFFF,
+                                              order, count, _ptr(dec), _ptr(out), ctypes.byref(cnt),
+                                              ctypes.byref(wit)))
+        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])),
+                         witness=None if wit.value == NO_WITNESS else int(wit.value))
+
+    def run_enum_device(self, params: Params, faulty_mask: int, order: int, count: int,
+                        d_decisions=0, d_outcome=0, d_counters=0, d_witness=0, stream=0):
+        """Enqueue strategies [params.first_trial, + count) on device pointers
+        (ba_enum_run_device); counters accumulated, the witness (uint64, set to NO_WITNESS
+        by the caller) min-accumulated.  The kernels are queued asynchronously, but the call
+        first copies the case's slot map from host memory and returns only after the
+        stream's earlier work has drained (include/ba.h)."""
+        _check(self.lib, self.lib.ba_enum_run_device(
+            self.handle, ctypes.byref(params), faulty_mask & 0xFFFFFFFF, order, count,
+            d_decisions or None, d_outcome or None, d_counters or None, d_witness or None,
+            stream or None))
 
     def stream(self) -> int:
         """The ctx's own HIP stream (ba_ctx_stream), as an int handle."""
@@ -607,6 +649,44 @@ def sm_coin_calls(n: int, m: int) -> int:
 def adv_paths(n: int, m: int) -> int:
     """Relay chains one receiver walks under a scripted policy: P(n-2, me) (ba_adv_paths)."""
     return int(load().ba_adv_paths(n, m))
+
+
+def enum_bits(n: int, m: int, faulty_mask: int) -> int:
+    """Free bits B of the case's strategy space (ba_enum_bits); 0xFFFFFFFF for bad n / m."""
+    return int(load().ba_enum_bits(n, m, faulty_mask & 0xFFFFFFFF))
+
+
+def enum_slots(n: int, m: int, faulty_mask: int) -> list:
+    """[(level, path rank)] of free bits 0..B-1 (ba_enum_slots)."""
+    lib = load()
+    level = np.zeros(ENUM_MAX_BITS, np.uint32)
+    slot = np.zeros(ENUM_MAX_BITS, np.uint64)
+    b = lib.ba_enum_slots(n, m, faulty_mask & 0xFFFFFFFF, level.ctypes.data, slot.ctypes.data,
+                          ENUM_MAX_BITS)
+    if b < 0:
+        raise BAError(b, lib.ba_last_error().decode())
+    return [(int(level[i]), int(slot[i])) for i in range(b)]
+
+
+def path_of_rank(n: int, level: int, rank: int) -> tuple:
+    """The relay path (0-based lieutenant ranks j_0..j_level) with lexicographic rank
+    `rank` among the (level+1)-permutations of the n-1 lieutenants (docs/SEMANTICS.md §2.2)."""
+    L = n - 1
+    digits = []
+    for i in range(level, -1, -1):  # the last step has L - level choices, the first L
+        rank, d = divmod(rank, L - i)
+        digits.append(d)
+    free, path = list(range(L)), []
+    for d in reversed(digits):
+        path.append(free.pop(d))
+    return tuple(path)
+
+
+def decode_strategy(n: int, m: int, faulty_mask: int, S: int) -> dict:
+    """{relay path: value} of the free slots under strategy S (docs/SEMANTICS.md §8): the
+    path's last lieutenant is the loyal recipient, the one before it (the commander for
+    a path of one) the traitor that sends it value 1 = attack / 0 = retreat."""
+    return {path_of_rank(n, k, x): (S >> i) & 1 for i, (k, x) in enumerate(enum_slots(n, m, faulty_mask))}
 
 
 def vote_slots(n: int, m: int, j_begin: int, j_end: int) -> int:

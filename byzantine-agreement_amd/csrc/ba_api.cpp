@@ -1216,6 +1216,233 @@ extern "C" int ba_adv_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t polic
     return BA_OK;
 }
 
+// ---------------------------------------------------------------------------
+// OM(m) against every traitor strategy of one case (docs/SEMANTICS.md §8; ba_enum.hip)
+// ---------------------------------------------------------------------------
+constexpr uint32_t kEnumBitsSaturated = 0xFFFFFFFEu;
+
+// B = [F_0](L - f_L) + f_L (L - f_L) sum_{k=1..me} P(L-2, k-1)
+extern "C" uint32_t ba_enum_bits(uint32_t n, uint32_t m, uint32_t faulty_mask) {
+    if (n < 1 || n > BA_MAX_GENERALS || m > BA_MAX_DEPTH) return 0xFFFFFFFFu;
+    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
+    const uint32_t F = faulty_mask & all;
+    const uint64_t L = n - 1, me = effective_depth(n, m);
+    const uint64_t fL = (uint64_t)__builtin_popcount(F >> 1), loyal = L - fL;
+    uint64_t chains = 0, p = 1;  // p = P(L-2, k-1)
+    for (uint64_t k = 1; k <= me; ++k) {
+        chains += p;
+        p *= L - 2 - (k - 1);  // k <= me <= L-1: the factor is >= 0, and 0 only after the last use
+    }
+    const uint64_t B = ((F & 1u) ? loyal : 0ull) + fL * loyal * chains;
+    return B > kEnumBitsSaturated ? kEnumBitsSaturated : (uint32_t)B;
+}
+
+// The slot classes of a case in (level ascending, path rank ascending) order.
+struct EnumPlan {
+    EnumCase g{};
+    std::vector<uint8_t> map;    // padded to 16 B
+    std::vector<uint32_t> level;  // free bit i -> its slot
+    std::vector<uint64_t> slot;
+};
+
+static int enum_plan(uint32_t n, uint32_t m, uint32_t faulty_mask, EnumPlan& pl) {
+    if (n < 1 || n > BA_MAX_GENERALS) return fail(BA_EINVAL, "n=%u outside [1,%d]", n, BA_MAX_GENERALS);
+    if (m > BA_MAX_DEPTH) return fail(BA_EINVAL, "m=%u > %d", m, BA_MAX_DEPTH);
+    const uint64_t slots = ba_tree_slots(n, m);
+    if (slots > kEnumMaxSlots)
+        return fail(BA_ETOOBIG, "n=%u m=%u: %llu tree slots > %u (the slot map must fit LDS)", n, m,
+                    (unsigned long long)slots, kEnumMaxSlots);
+    const uint32_t B = ba_enum_bits(n, m, faulty_mask);
+    if (B > BA_ENUM_MAX_BITS)
+        return fail(BA_ETOOBIG, "n=%u m=%u faulty_mask=0x%x: %u free bits > %d", n, m, faulty_mask, B,
+                    BA_ENUM_MAX_BITS);
+    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
+    const uint32_t F = faulty_mask & all, L = n - 1, me = effective_depth(n, m);
+    pl.g.n = n;
+    pl.g.fmask = F;
+    std::vector<std::vector<uint8_t>> cls(me + 1);  // per level, in path rank
+    // depth-first over the relay paths in lexicographic order: each level's slots come
+    // out in rank order.  sender: general index of the slot's sender.
+    struct Walk {
+        uint32_t L, me, F;
+        std::vector<std::vector<uint8_t>>& cls;
+        void go(uint32_t k, uint32_t used, uint32_t sender) {
+            for (uint32_t j = 0; j < L; ++j) {
+                if ((used >> j) & 1u) continue;
+                const bool fs = (F >> sender) & 1u, fr = (F >> (j + 1)) & 1u;
+                cls[k].push_back(!fs ? (uint8_t)kEnumTruth : (fr ? (uint8_t)kEnumDead : (uint8_t)0));
+                if (k < me) go(k + 1, used | (1u << j), j + 1);
+            }
+        }
+    } walk{L, me, F, cls};
+    if (L > 0) walk.go(0, 0, 0);
+    pl.map.clear();
+    pl.level.clear();
+    pl.slot.clear();
+    for (int k = 0; k < kEnumLevels; ++k) pl.g.off[k] = 0;
+    uint32_t bit = 0;
+    for (uint32_t k = 0; k <= me; ++k) {
+        pl.g.off[k] = (uint32_t)pl.map.size();
+        for (uint64_t x = 0; x < cls[k].size(); ++x) {
+            uint8_t c = cls[k][x];
+            if (c == 0) {
+                c = (uint8_t)bit++;
+                pl.level.push_back(k);
+                pl.slot.push_back(x);
+            }
+            pl.map.push_back(c);
+        }
+    }
+    if (bit != B || pl.map.size() != (L > 0 ? slots : 0))
+        return fail(BA_EINVAL, "internal: %u free slots counted, formula %u", bit, B);
+    pl.map.resize((pl.map.size() + 15) & ~(size_t)15, (uint8_t)kEnumDead);
+    pl.g.map_bytes = (uint32_t)pl.map.size();
+    return BA_OK;
+}
+
+extern "C" int ba_enum_slots(uint32_t n, uint32_t m, uint32_t faulty_mask, uint32_t* level,
+                             uint64_t* slot, uint32_t cap) {
+    EnumPlan pl;
+    int rc = enum_plan(n, m, faulty_mask, pl);
+    if (rc != BA_OK) return rc;
+    const uint32_t B = (uint32_t)pl.level.size();
+    if (B > cap) return fail(BA_EINVAL, "cap=%u < %u free bits", cap, B);
+    if (B && (!level || !slot)) return fail(BA_EINVAL, "level and slot are required");
+    for (uint32_t i = 0; i < B; ++i) {
+        level[i] = pl.level[i];
+        slot[i] = pl.slot[i];
+    }
+    return (int)B;
+}
+
+// One launch takes at most 2^40 strategies: the counter sink's per-launch sums
+// (at most 31 decisions per strategy) stay below 2^48.
+constexpr uint64_t kEnumLaunchMax = 1ull << 40;
+
+static int validate_enum(const ba_params* p, uint32_t faulty_mask, uint32_t order, uint64_t batch,
+                         EnumPlan& pl) {
+    if (!p) return fail(BA_EINVAL, "params is NULL");
+    if (p->lie_mode == BA_LIE_TABLE)
+        return fail(BA_ENOTSUP, "the enumeration draws no coins (no table mode)");
+    int rc = validate(p, batch, true, true, false);
+    if (rc != BA_OK) return rc;
+    if (p->engine != BA_ENGINE_AUTO)
+        return fail(BA_EINVAL, "engine=%u: the enumeration has one engine (BA_ENGINE_AUTO)", p->engine);
+    if (p->faulty_mode != BA_FAULTY_GIVEN || p->order_mode != BA_ORDER_GIVEN)
+        return fail(BA_EINVAL, "faulty_mode=%u order_mode=%u: one given faulty set and order per call "
+                    "(BA_FAULTY_GIVEN, BA_ORDER_GIVEN)", p->faulty_mode, p->order_mode);
+    if (order > BA_OTHER) return fail(BA_EINVAL, "order=%u", order);
+    if ((rc = enum_plan(p->n, p->m, faulty_mask, pl)) != BA_OK) return rc;
+    pl.g.order = order;
+    const uint64_t space = 1ull << pl.level.size();  // B <= 48
+    if (p->first_trial > space || batch > space - p->first_trial)
+        return fail(BA_EINVAL, "strategies [%llu, %llu + %llu) reach past 2^%u",
+                    (unsigned long long)p->first_trial, (unsigned long long)p->first_trial,
+                    (unsigned long long)batch, (unsigned)pl.level.size());
+    return BA_OK;
+}
+
+// The case's slot map into the ctx's scratch, on `stream` (in the ctx's call order: the
+// caller has ordered the stream).  The source is pageable host memory that dies with the
+// plan: hipMemcpyAsync has read it when it returns, which it can only do by completing
+// the copy first, so this call waits on the host for the stream's earlier work
+// (include/ba.h says so).
+static int enum_upload(ba_ctx* ctx, const EnumPlan& pl, hipStream_t stream) {
+    const size_t mb = pl.map.size() < 16 ? 16 : pl.map.size();
+    int rc = ctx->scratch.grow(mb);
+    if (rc != BA_OK) return rc;
+    if (!pl.map.empty())
+        HIP_TRY(hipMemcpyAsync(ctx->scratch.p, pl.map.data(), pl.map.size(), hipMemcpyHostToDevice,
+                               stream));
+    return BA_OK;
+}
+
+// Strategies [first, first + batch) of an uploaded case, kEnumLaunchMax per launch.
+static int enum_launch_range(ba_ctx* ctx, const ba_params* p, const EnumPlan& pl, uint64_t first,
+                             uint64_t batch, uint64_t* d_decisions, uint8_t* d_outcome,
+                             uint64_t* d_counters, uint64_t* d_witness, void* stream) {
+    ba_params q = *p;
+    for (uint64_t t0 = 0; t0 < batch; t0 += kEnumLaunchMax) {
+        const uint64_t nt = batch - t0 < kEnumLaunchMax ? batch - t0 : kEnumLaunchMax;
+        q.first_trial = first + t0;
+        const RunArgs a = make_args(ctx, &q, nt, nullptr, nullptr, nullptr, nullptr,
+                                    d_decisions ? d_decisions + t0 : nullptr,
+                                    d_outcome ? d_outcome + t0 : nullptr, d_counters, stream);
+        HIP_TRY(launch_enum(a, pl.g, (const uint8_t*)ctx->scratch.p, d_witness));
+    }
+    return BA_OK;
+}
+
+extern "C" int ba_enum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t faulty_mask,
+                                  uint32_t order, uint64_t batch, uint64_t* d_decisions,
+                                  uint8_t* d_outcome, uint64_t* d_counters, uint64_t* d_witness,
+                                  void* stream) {
+    return ordered(ctx, stream, [&] {
+        EnumPlan pl;
+        int rc = validate_enum(p, faulty_mask, order, batch, pl);
+        if (rc != BA_OK) return rc;
+        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
+        if (batch == 0) return BA_OK;
+        if ((rc = enum_upload(ctx, pl, (hipStream_t)stream)) != BA_OK) return rc;
+        return enum_launch_range(ctx, p, pl, p->first_trial, batch, d_decisions, d_outcome,
+                                 d_counters, d_witness, stream);
+    });
+}
+
+// Host entry: run, copy out, in chunks of at most kEnumHostChunk strategies when a
+// per-trial output is asked for, so the ctx's staging buffers stay bounded (counters
+// and the witness accumulate across the chunks on the device); counters only: one
+// chunk.  The case is planned and its slot map uploaded once for all the chunks.
+constexpr uint64_t kEnumHostChunk = 1ull << 24;
+
+extern "C" int ba_enum_run(ba_ctx* ctx, const ba_params* p, uint32_t faulty_mask, uint32_t order,
+                           uint64_t batch, uint64_t* decisions, uint8_t* outcome,
+                           ba_counters* counters, uint64_t* witness) {
+    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
+    EnumPlan pl;
+    int rc = validate_enum(p, faulty_mask, order, batch, pl);
+    if (rc != BA_OK) return rc;
+    if (counters) memset(counters, 0, sizeof *counters);
+    if (witness) *witness = UINT64_MAX;
+    if (batch == 0) return BA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx_order(ctx, st));  // the io buffers follow the ctx's last call
+    uint64_t chunk = (decisions || outcome) ? kEnumHostChunk : batch;
+    if (const char* e = getenv("BA_ENUM_HOST_CHUNK")) {  // tests: chunk a small batch (multiple of 64)
+        const uint64_t c = strtoull(e, nullptr, 0) & ~63ull;
+        if (c) chunk = c;
+    }
+    if (chunk > batch) chunk = batch;
+    if (decisions && (rc = ctx->io_dec.grow(chunk * 8)) != BA_OK) return rc;
+    if (outcome && (rc = ctx->io_out.grow(chunk)) != BA_OK) return rc;
+    // the counters, then the witness in the word after them
+    if ((rc = ctx->io_cnt.grow((BA_NCOUNTERS + 1) * 8)) != BA_OK) return rc;
+    uint64_t* d_cnt = (uint64_t*)ctx->io_cnt.p;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, BA_NCOUNTERS * 8, st));
+    HIP_TRY(hipMemsetAsync(d_cnt + BA_NCOUNTERS, 0xFF, 8, st));
+    rc = enum_upload(ctx, pl, st);
+    (void)ctx_mark(ctx, st);  // whatever follows: work of this ctx is queued on st
+    if (rc != BA_OK) return rc;
+    for (uint64_t t0 = 0; t0 < batch; t0 += chunk) {
+        const uint64_t nt = batch - t0 < chunk ? batch - t0 : chunk;
+        rc = enum_launch_range(ctx, p, pl, p->first_trial + t0, nt,
+                               decisions ? (uint64_t*)ctx->io_dec.p : nullptr,
+                               outcome ? (uint8_t*)ctx->io_out.p : nullptr, d_cnt,
+                               d_cnt + BA_NCOUNTERS, st);
+        if (rc != BA_OK) return rc;
+        if (decisions)
+            HIP_TRY(hipMemcpyAsync(decisions + t0, ctx->io_dec.p, nt * 8, hipMemcpyDeviceToHost, st));
+        if (outcome) HIP_TRY(hipMemcpyAsync(outcome + t0, ctx->io_out.p, nt, hipMemcpyDeviceToHost, st));
+    }
+    uint64_t h_cnt[BA_NCOUNTERS + 1];
+    HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (counters) memcpy(counters->v, h_cnt, BA_NCOUNTERS * 8);
+    if (witness) *witness = h_cnt[BA_NCOUNTERS];
+    return BA_OK;
+}
+
 extern "C" int ba_split_votes_device(ba_ctx* ctx, const ba_params* p, uint64_t batch,
                                      uint32_t level, uint32_t u_begin, uint32_t u_end,
                                      const uint32_t* d_faulty, const uint8_t* d_order,

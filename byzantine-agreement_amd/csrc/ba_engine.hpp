@@ -199,4 +199,18 @@ hipError_t launch_sm(const RunArgs& a, uint64_t* vsets);
 // thread per (64-trial word, receiver), no lie draws.  policy: BA_ADV_*.
 hipError_t launch_adv(const RunArgs& a, uint32_t policy);
 
+// OM(m) against every traitor strategy of one case (ba_enum.hip, docs/SEMANTICS.md
+// §8): trial t is strategy S = t.  The slot map holds one byte per tree slot, level
+// k at off[k] in lexicographic path rank: the free bit's index, kEnumTruth (loyal
+// sender) or kEnumDead (faulty sender and recipient).
+constexpr uint32_t kEnumMaxSlots = 4096;  // the map fits LDS
+constexpr int kEnumLevels = 9;            // levels 0..8
+constexpr uint32_t kEnumTruth = 0xFE, kEnumDead = 0xFF;
+struct EnumCase {
+    uint32_t n, fmask, order;  // fmask masked to n bits; order code 0..2
+    uint32_t map_bytes;        // the map's size rounded up to 16 B
+    uint32_t off[kEnumLevels];
+};
+hipError_t launch_enum(const RunArgs& a, const EnumCase& g, const uint8_t* d_map, uint64_t* witness);
+
 }  // namespace ba

@@ -301,6 +301,52 @@ int ba_adv_run_trials_device(struct ba_ctx* ctx, const ba_params* p, uint32_t po
  * n outside 1..32 or m > 8. */
 uint64_t ba_adv_paths(uint32_t n, uint32_t m);   /* host only */
 
+/* ---- OM(m) against every traitor strategy of one case ---------------------------
+ * A policy is one adversary; Lamport's theorem speaks of every choice of messages.
+ * These entries walk all of them for one case (n, m, faulty set, order)
+ * (docs/SEMANTICS.md §8; no ba.py analogue).  Every message a traitor sends to a
+ * LOYAL lieutenant is a free bit; a message between two traitors is retreat (it
+ * cannot change a loyal lieutenant's decision, §8); a loyal sender relays the
+ * truth.  A strategy S is an assignment of the B = ba_enum_bits(n, m, faulty_mask)
+ * free bits: bit i of S is the value of the i-th free slot in (level ascending,
+ * lexicographic path rank ascending) order, 1 = attack (ba_enum_slots lists them).
+ * Trial t of a call is strategy S = t: a call covers S in [p->first_trial,
+ * p->first_trial + batch), first_trial a multiple of 64, ending at or below 2^B
+ * (else BA_EINVAL).  p supplies n, m and first_trial; seed and f are unused.
+ * p->lie_mode must be BA_LIE_PHILOX (TABLE: BA_ENOTSUP), p->engine BA_ENGINE_AUTO,
+ * p->faulty_mode BA_FAULTY_GIVEN and p->order_mode BA_ORDER_GIVEN (else BA_EINVAL):
+ * the one faulty_mask (masked to n bits) and the one order code (<= BA_OTHER, else
+ * BA_EINVAL) of all the call's trials are arguments.  B > BA_ENUM_MAX_BITS and
+ * ba_tree_slots(n, m) > 4096 are BA_ETOOBIG.  decisions / outcome / counters: the
+ * OM layouts above, faulty lieutenants deciding on their dead slots at retreat.
+ * witness: the smallest S of the range that violates IC1 or (IC2 applicable) IC2,
+ * in bound or not, or 2^64 - 1 when none does.  batch = 0: BA_OK, zero counters,
+ * witness 2^64 - 1.  Every call copies the case's slot map (at most 4 KiB) from
+ * pageable host memory to the device on the call's stream.  The HIP runtime finishes
+ * such a copy before it returns, so ba_enum_run_device is NOT fully asynchronous: it
+ * returns after the stream's earlier work has drained and the map has landed, with
+ * its own launches queued behind.  For the same reason do not capture these entries
+ * into a graph.  (ba_enum_run plans the case and copies the map once, whatever the
+ * number of its output chunks.) */
+#define BA_ENUM_MAX_BITS 48
+/* B; host only.  0xFFFFFFFF for n outside 1..32 or m > 8; saturates at 0xFFFFFFFE. */
+uint32_t ba_enum_bits(uint32_t n, uint32_t m, uint32_t faulty_mask);
+/* bit i -> (level[i], slot[i] = path rank in that level); host only.  Returns B, or
+ * BA_EINVAL (bad n / m, cap < B), BA_ETOOBIG (the two caps). */
+int ba_enum_slots(uint32_t n, uint32_t m, uint32_t faulty_mask, uint32_t* level, uint64_t* slot,
+                  uint32_t cap);
+int ba_enum_run(struct ba_ctx* ctx, const ba_params* p, uint32_t faulty_mask, uint32_t order,
+                uint64_t batch, uint64_t* decisions, uint8_t* outcome, ba_counters* counters,
+                uint64_t* witness);  /* counters and witness overwritten */
+/* The same walk on device buffers, enqueued on `stream` in the ctx's call order
+ * (NULL = HIP's null stream).  d_counters is accumulated into; d_witness (optional)
+ * is min-accumulated: the caller sets it to 2^64 - 1 first.  The launches are
+ * asynchronous; the call itself waits for the stream's earlier work (the map copy,
+ * above). */
+int ba_enum_run_device(struct ba_ctx* ctx, const ba_params* p, uint32_t faulty_mask,
+                       uint32_t order, uint64_t batch, uint64_t* d_decisions, uint8_t* d_outcome,
+                       uint64_t* d_counters, uint64_t* d_witness, void* stream);
+
 /* ---- one huge instance split by first-hop subtree --------
  * The subtree of first-hop lieutenant j (relay paths starting 0 -> j) needs
  * only L_0[j]; its relay levels and inner majorities are independent of the
