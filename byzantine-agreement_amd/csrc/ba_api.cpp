@@ -1217,6 +1217,111 @@ extern "C" int ba_adv_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t polic
 }
 
 // ---------------------------------------------------------------------------
+// Phase King (docs/SEMANTICS.md §9; ba_king.hip)
+// ---------------------------------------------------------------------------
+// P = min(m, n-1) + 1 <= n: the kings, generals 0..P-1, are distinct
+extern "C" uint32_t ba_king_phases(uint32_t n, uint32_t m) {
+    if (n < 1 || n > BA_MAX_GENERALS || m > BA_MAX_DEPTH) return 0;
+    return (m < n - 1 ? m : n - 1) + 1;
+}
+
+// ceil(n/2) calls serve one sender's n recipients: the commander's send, and per
+// phase n senders' exchange messages and the king's
+extern "C" uint64_t ba_king_coin_calls(uint32_t n, uint32_t m) {
+    const uint64_t P = ba_king_phases(n, m);
+    if (P == 0) return 0;
+    return (uint64_t)((n + 1) / 2) * (1 + P * (n + 1));
+}
+
+static int validate_king(const ba_params* p, uint32_t policy, uint64_t batch, bool has_faulty,
+                         bool has_order) {
+    if (!p) return fail(BA_EINVAL, "params is NULL");
+    if (p->lie_mode == BA_LIE_TABLE)
+        return fail(BA_ENOTSUP, "Phase King draws its coins from Philox only (no table mode)");
+    int rc = validate(p, batch, has_faulty, has_order, false);
+    if (rc != BA_OK) return rc;
+    if (p->engine != BA_ENGINE_AUTO)
+        return fail(BA_EINVAL, "engine=%u: Phase King has one engine (BA_ENGINE_AUTO)", p->engine);
+    if (policy > BA_KING_SPLIT) return fail(BA_EINVAL, "policy=%u", policy);
+    return BA_OK;
+}
+
+extern "C" int ba_king_run_trials_device(ba_ctx* ctx, const ba_params* p, uint32_t policy,
+                                         uint64_t batch, const uint32_t* d_faulty,
+                                         const uint8_t* d_order, uint64_t* d_decisions,
+                                         uint8_t* d_outcome, uint8_t* d_settled,
+                                         uint64_t* d_counters, void* stream) {
+    return ordered(ctx, stream, [&] {
+        int rc = validate_king(p, policy, batch, d_faulty != nullptr, d_order != nullptr);
+        if (rc != BA_OK) return rc;
+        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
+        if (batch == 0) return BA_OK;
+        const RunArgs a = make_args(ctx, p, batch, d_faulty, d_order, nullptr, nullptr, d_decisions,
+                                    d_outcome, d_counters, stream);
+        HIP_TRY(launch_king(a, policy, ba_king_phases(p->n, p->m), d_settled));
+        return BA_OK;
+    });
+}
+
+// Host entry: copy in, run, copy out, in chunks of at most kKingHostChunk trials so
+// the ctx's staging buffers stay bounded whatever the batch (counters accumulate
+// across the chunks on the device).
+constexpr uint64_t kKingHostChunk = 1ull << 24;
+
+extern "C" int ba_king_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
+                                  const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
+                                  uint8_t* outcome, uint8_t* settled, ba_counters* counters) {
+    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
+    int rc = validate_king(p, policy, batch, faulty != nullptr, order != nullptr);
+    if (rc != BA_OK) return rc;
+    if (counters) memset(counters, 0, sizeof *counters);
+    if (batch == 0) return BA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx_order(ctx, st));  // the io buffers follow the ctx's last call
+    const bool need_f = p->faulty_mode == BA_FAULTY_GIVEN, need_o = p->order_mode == BA_ORDER_GIVEN;
+    uint64_t chunk = kKingHostChunk;
+    if (const char* e = getenv("BA_KING_HOST_CHUNK")) {  // tests: chunk a small batch (multiple of 64)
+        const uint64_t c = strtoull(e, nullptr, 0) & ~63ull;
+        if (c) chunk = c;
+    }
+    if (chunk > batch) chunk = batch;
+    if (need_f && (rc = ctx->io_faulty.grow(chunk * 4)) != BA_OK) return rc;
+    if (need_o && (rc = ctx->io_order.grow(chunk)) != BA_OK) return rc;
+    if (decisions && (rc = ctx->io_dec.grow(chunk * 8)) != BA_OK) return rc;
+    // outcome and settled bytes share io_out: [chunk] outcome, then [chunk] settled
+    if ((outcome || settled) && (rc = ctx->io_out.grow(chunk * 2)) != BA_OK) return rc;
+    if ((rc = ctx->io_cnt.grow(BA_NCOUNTERS * 8)) != BA_OK) return rc;
+    uint8_t* d_out = (uint8_t*)ctx->io_out.p;
+    uint8_t* d_set = d_out ? d_out + chunk : nullptr;
+    HIP_TRY(hipMemsetAsync(ctx->io_cnt.p, 0, BA_NCOUNTERS * 8, st));
+    ba_params q = *p;
+    for (uint64_t t0 = 0; t0 < batch; t0 += chunk) {
+        const uint64_t nt = batch - t0 < chunk ? batch - t0 : chunk;
+        q.first_trial = p->first_trial + t0;
+        if (need_f)
+            HIP_TRY(hipMemcpyAsync(ctx->io_faulty.p, faulty + t0, nt * 4, hipMemcpyHostToDevice, st));
+        if (need_o) HIP_TRY(hipMemcpyAsync(ctx->io_order.p, order + t0, nt, hipMemcpyHostToDevice, st));
+        rc = ba_king_run_trials_device(ctx, &q, policy, nt,
+                                       need_f ? (const uint32_t*)ctx->io_faulty.p : nullptr,
+                                       need_o ? (const uint8_t*)ctx->io_order.p : nullptr,
+                                       decisions ? (uint64_t*)ctx->io_dec.p : nullptr,
+                                       outcome ? d_out : nullptr, settled ? d_set : nullptr,
+                                       (uint64_t*)ctx->io_cnt.p, st);
+        if (rc != BA_OK) return rc;
+        if (decisions)
+            HIP_TRY(hipMemcpyAsync(decisions + t0, ctx->io_dec.p, nt * 8, hipMemcpyDeviceToHost, st));
+        if (outcome) HIP_TRY(hipMemcpyAsync(outcome + t0, d_out, nt, hipMemcpyDeviceToHost, st));
+        if (settled) HIP_TRY(hipMemcpyAsync(settled + t0, d_set, nt, hipMemcpyDeviceToHost, st));
+    }
+    uint64_t h_cnt[BA_NCOUNTERS];
+    HIP_TRY(hipMemcpyAsync(h_cnt, ctx->io_cnt.p, BA_NCOUNTERS * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (counters) memcpy(counters->v, h_cnt, sizeof h_cnt);
+    return BA_OK;
+}
+
+// ---------------------------------------------------------------------------
 // OM(m) against every traitor strategy of one case (docs/SEMANTICS.md §8; ba_enum.hip)
 // ---------------------------------------------------------------------------
 constexpr uint32_t kEnumBitsSaturated = 0xFFFFFFFEu;

@@ -213,4 +213,9 @@ struct EnumCase {
 };
 hipError_t launch_enum(const RunArgs& a, const EnumCase& g, const uint8_t* d_map, uint64_t* witness);
 
+// Phase King (ba_king.hip, docs/SEMANTICS.md §9): one wave per 64-trial word; a.m is
+// the parameter m of the strong threshold and of the in-bound rule, phases = P.
+// policy: BA_KING_*.  settled optional.
+hipError_t launch_king(const RunArgs& a, uint32_t policy, uint32_t phases, uint8_t* settled);
+
 }  // namespace ba

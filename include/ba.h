@@ -347,6 +347,59 @@ int ba_enum_run_device(struct ba_ctx* ctx, const ba_params* p, uint32_t faulty_m
                        uint32_t order, uint64_t batch, uint64_t* d_decisions, uint8_t* d_outcome,
                        uint64_t* d_counters, uint64_t* d_witness, void* stream);
 
+/* ---- Phase King: unsigned, polynomial ------------------------------------------
+ * Berman, Garay and Perry's protocol (docs/SEMANTICS.md §9; no ba.py analogue): oral
+ * messages like OM(m), but (m+1) n^2 one-bit messages where OM's relay tree has
+ * P(n-1, m+1) leaves, at the price of the bound n > 4m.  Every general, the
+ * commander included, keeps one preference bit and runs the rules honestly; being
+ * faulty only replaces what a general sends.
+ *   round 0      the commander sends its order; each lieutenant's preference is
+ *                what it was shown, the commander's its order bit;
+ *   phase p      p = 1..P, P = ba_king_phases(n, m) = min(m, n-1) + 1, king = general
+ *                p-1.  Exchange: everyone sends its preference to everyone; general i
+ *                counts the attack votes c1 of all n generals (its own true value
+ *                included), maj = [2 c1 > n], mult = the majority's count, strong =
+ *                [2 mult > n + 2m] (the parameter m).  King: the king sends its maj;
+ *                i keeps maj if strong, else takes the king's value (the king its own);
+ *   decision     lieutenant r decides its preference after phase P (never undefined),
+ *                then ba.py's quorum and the IC1/IC2 flags over the commander's order
+ *                and the lieutenants' decisions, as everywhere else.
+ * A faulty sender j shows recipient r, in place of the truth, under
+ *   BA_KING_COIN   the coin c(q, 32 j + r) = coin(128 + q, 32 j + r) of the OM lie
+ *                  stream, q = 0 the commander's send, 2p-1 / 2p phase p's rounds;
+ *   BA_KING_SPLIT  r & 1: attack to odd general indices, retreat to even ones, in
+ *                  every round (no coin is drawn).
+ * Neither is the worst case: rates beyond the bound are rates against these two.
+ * In-bound means |F| <= m and n > 4m (BA_C_IN_BOUND / BA_C_BOUND_VIOL follow it);
+ * BA_C_UNDEF_DECISIONS is always 0.  The synthetic inputs are ba_run_trials' own: an
+ * OM, SM and KING run with equal params see the same faulty sets and orders.
+ * p->lie_mode must be BA_LIE_PHILOX (TABLE: BA_ENOTSUP), p->engine BA_ENGINE_AUTO,
+ * policy <= BA_KING_SPLIT (else BA_EINVAL); every faulty/order mode, first_trial and
+ * seed as in ba_run_trials.  decisions / outcome / counters: the layouts above.
+ * settled[t] (optional, uint8): the smallest p in 0..P such that all loyal generals
+ * (a loyal commander included) hold one common preference at the end of phase p and
+ * of every later phase (phase 0 = round 0; none or one loyal general agrees), or 255
+ * if they differ after phase P. */
+#define BA_KING_COIN 0
+#define BA_KING_SPLIT 1
+int ba_king_run_trials(struct ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
+                       const uint32_t* faulty_mask, const uint8_t* order, uint64_t* decisions,
+                       uint8_t* outcome, uint8_t* settled,
+                       ba_counters* counters);             /* counters overwritten */
+/* The same rounds on device buffers, enqueued on `stream` in the ctx's call order
+ * (NULL = HIP's null stream). */
+int ba_king_run_trials_device(struct ba_ctx* ctx, const ba_params* p, uint32_t policy,
+                              uint64_t batch, const uint32_t* d_faulty_mask,
+                              const uint8_t* d_order, uint64_t* d_decisions, uint8_t* d_outcome,
+                              uint8_t* d_settled, uint64_t* d_counters,
+                              void* stream);               /* accumulated, async */
+/* ceil(n/2) (1 + P (n+1)): Philox calls per 64-trial word when every sender is faulty
+ * somewhere in the word (one call serves recipients r and r ^ 1 of one sender).  0 for
+ * n outside 1..32 or m > 8. */
+uint64_t ba_king_coin_calls(uint32_t n, uint32_t m);   /* host only */
+/* P = min(m, n-1) + 1; 0 for n outside 1..32 or m > 8. */
+uint32_t ba_king_phases(uint32_t n, uint32_t m);       /* host only */
+
 /* ---- one huge instance split by first-hop subtree --------
  * The subtree of first-hop lieutenant j (relay paths starting 0 -> j) needs
  * only L_0[j]; its relay levels and inner majorities are independent of the
