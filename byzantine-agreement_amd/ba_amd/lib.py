@@ -30,7 +30,7 @@ Q_RETREAT, Q_ATTACK, Q_UNDETERMINED = 0, 1, 2
 ENGINE_AUTO, ENGINE_FUSED, ENGINE_LEVELS = 0, 1, 2
 SPLIT_FIRST_HOP, SPLIT_SECOND_HOP = 1, 2
 ADV_SPLIT, ADV_FLIP, ADV_ANTI = 0, 1, 2  # scripted traitor policies (docs/SEMANTICS.md §7)
-KING_COIN, KING_SPLIT = 0, 1  # Phase King's faulty senders (docs/SEMANTICS.md §9)
+KING_COIN, KING_SPLIT = 0, 1  # Phase King's and KING3's faulty senders (docs/SEMANTICS.md §9, §10)
 KING_UNSETTLED = 255  # RunResult.settled: the loyal generals differ after the last phase
 COUNTER_NAMES = ["trials", "agreement", "validity_applicable", "validity", "quorum_retreat",
                  "quorum_attack", "quorum_undetermined", "undefined_decisions", "in_bound",
@@ -51,7 +51,8 @@ EXPORTS = ["ba_version", "ba_device_count", "ba_ctx_create", "ba_ctx_destroy", "
            "ba_adv_run_trials", "ba_adv_run_trials_device", "ba_adv_paths",
            "ba_enum_bits", "ba_enum_slots", "ba_enum_run", "ba_enum_run_device",
            "ba_king_run_trials", "ba_king_run_trials_device", "ba_king_coin_calls",
-           "ba_king_phases"]
+           "ba_king_phases", "ba_king3_run_trials", "ba_king3_run_trials_device",
+           "ba_king3_coin_calls", "ba_king3_phases"]
 ENUM_MAX_BITS = 48  # BA_ENUM_MAX_BITS (docs/SEMANTICS.md §8)
 NO_WITNESS = (1 << 64) - 1
 PROBE_BLOCKS = 2048  # BA_PROBE_BLOCKS
@@ -199,6 +200,12 @@ def load(path: str | None = None):
     lib.ba_king_coin_calls.restype = u64
     lib.ba_king_phases.argtypes = [u32, u32]
     lib.ba_king_phases.restype = u32
+    lib.ba_king3_run_trials.argtypes = lib.ba_king_run_trials.argtypes
+    lib.ba_king3_run_trials_device.argtypes = lib.ba_king_run_trials_device.argtypes
+    lib.ba_king3_coin_calls.argtypes = [u32, u32]
+    lib.ba_king3_coin_calls.restype = u64
+    lib.ba_king3_phases.argtypes = [u32, u32]
+    lib.ba_king3_phases.restype = u32
     if lib.ba_version() != ABI_VERSION:
         raise RuntimeError(f"libba_hip ABI {lib.ba_version()} != {ABI_VERSION}")
     if path is None:
@@ -251,7 +258,7 @@ class RunResult:
     counters: dict = field(default_factory=dict)
     vsets: np.ndarray | None = None  # run_sm(want_vsets=True): bits 2(r-1) attack, 2(r-1)+1 retreat in V_r
     witness: int | None = None  # run_enum: the smallest violating strategy, None when there is none
-    settled: np.ndarray | None = None  # run_king(want_settled=True): phase from which the loyal agree, 255 = never
+    settled: np.ndarray | None = None  # run_king / run_king3(want_settled=True): phase from which the loyal agree, 255 = never
 
     def decision(self, t: int, r: int) -> int:
         """Decision code of lieutenant r (1..n-1) in trial t."""
@@ -393,6 +400,35 @@ class Engine:
         """Enqueue Phase King trials on device pointers (ba_king_run_trials_device);
         asynchronous, counters accumulated."""
         _check(self.lib, self.lib.ba_king_run_trials_device(
+            self.handle, ctypes.byref(params), policy, batch, d_faulty or None, d_order or None,
+            d_decisions or None, d_outcome or None, d_settled or None, d_counters or None,
+            stream or None))
+
+    def run_king3(self, n, m, batch, policy=KING_COIN, seed=0, lie_mode=LIE_PHILOX,
+                  faulty_mode=FAULTY_GIVEN, f=0, order_mode=ORDER_GIVEN, order_value=ATTACK,
+                  engine=ENGINE_AUTO, first_trial=0, faulty=None, order=None, want_decisions=True,
+                  want_outcome=True, want_settled=False) -> RunResult:
+        """Resolve `batch` trials of the three-round King algorithm (KING_COIN, KING_SPLIT;
+        docs/SEMANTICS.md §10; m <= 10) through host buffers; the same inputs as `run`
+        and `run_king` with equal keywords."""
+        faulty = None if faulty is None else np.ascontiguousarray(faulty, dtype=np.uint32)
+        order = None if order is None else np.ascontiguousarray(order, dtype=np.uint8)
+        dec = np.zeros(batch, np.uint64) if want_decisions else None
+        out = np.zeros(batch, np.uint8) if want_outcome else None
+        stl = np.zeros(batch, np.uint8) if want_settled else None
+        p = make_params(n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, engine,
+                        first_trial)
+        cnt = Counters()
+        _check(self.lib, self.lib.ba_king3_run_trials(self.handle, ctypes.byref(p), policy, batch,
+                                                      _ptr(faulty), _ptr(order), _ptr(dec), _ptr(out),
+                                                      _ptr(stl), ctypes.byref(cnt)))
+        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])), settled=stl)
+
+    def run_king3_device(self, params: Params, batch: int, policy: int, d_faulty=0, d_order=0,
+                         d_decisions=0, d_outcome=0, d_settled=0, d_counters=0, stream=0):
+        """Enqueue three-round King trials on device pointers (ba_king3_run_trials_device);
+        asynchronous, counters accumulated."""
+        _check(self.lib, self.lib.ba_king3_run_trials_device(
             self.handle, ctypes.byref(params), policy, batch, d_faulty or None, d_order or None,
             d_decisions or None, d_outcome or None, d_settled or None, d_counters or None,
             stream or None))
@@ -691,6 +727,17 @@ def king_coin_calls(n: int, m: int) -> int:
     """Philox calls Phase King makes per 64-trial word: ceil(n/2) (1 + P (n + 1))
     (ba_king_coin_calls)."""
     return int(load().ba_king_coin_calls(n, m))
+
+
+def king3_coin_calls(n: int, m: int) -> int:
+    """Philox calls per 64-trial word of k_king3 when every sender is faulty in the word
+    (ba_king3_coin_calls)."""
+    return int(load().ba_king3_coin_calls(n, m))
+
+
+def king3_phases(n: int, m: int) -> int:
+    """P = min(m, n - 1) + 1 phases (ba_king3_phases); 0 for n outside 1..32 or m > 10."""
+    return int(load().ba_king3_phases(n, m))
 
 
 def king_phases(n: int, m: int) -> int:

@@ -479,11 +479,12 @@ extern "C" int ba_engine_for(uint32_t n, uint32_t m) {
 // ---------------------------------------------------------------------------
 // validation
 // ---------------------------------------------------------------------------
+// max_m: the protocol's own limit on m (BA_MAX_DEPTH everywhere but KING3)
 static int validate(const ba_params* p, uint64_t batch, bool has_faulty, bool has_order,
-                    bool has_table) {
+                    bool has_table, uint32_t max_m = BA_MAX_DEPTH) {
     if (!p) return fail(BA_EINVAL, "params is NULL");
     if (p->n < 1 || p->n > BA_MAX_GENERALS) return fail(BA_EINVAL, "n=%u outside [1,%d]", p->n, BA_MAX_GENERALS);
-    if (p->m > BA_MAX_DEPTH) return fail(BA_EINVAL, "m=%u > %d", p->m, BA_MAX_DEPTH);
+    if (p->m > max_m) return fail(BA_EINVAL, "m=%u > %u", p->m, max_m);
     if (p->lie_mode > BA_LIE_TABLE) return fail(BA_EINVAL, "lie_mode=%u", p->lie_mode);
     if (p->faulty_mode > BA_FAULTY_EXACT) return fail(BA_EINVAL, "faulty_mode=%u", p->faulty_mode);
     if (p->order_mode > BA_ORDER_CONST) return fail(BA_EINVAL, "order_mode=%u", p->order_mode);
@@ -1263,16 +1264,22 @@ extern "C" int ba_king_run_trials_device(ba_ctx* ctx, const ba_params* p, uint32
     });
 }
 
-// Host entry: copy in, run, copy out, in chunks of at most kKingHostChunk trials so
-// the ctx's staging buffers stay bounded whatever the batch (counters accumulate
-// across the chunks on the device).
+// Host entry of Phase King and KING3: copy in, run, copy out, in chunks of at most
+// kKingHostChunk trials so the ctx's staging buffers stay bounded whatever the batch
+// (counters accumulate across the chunks on the device).  `check` is the protocol's
+// validation, `device_entry` its device entry, `chunk_env` the tests' chunk override.
 constexpr uint64_t kKingHostChunk = 1ull << 24;
 
-extern "C" int ba_king_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
-                                  const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
-                                  uint8_t* outcome, uint8_t* settled, ba_counters* counters) {
+using KingValidate = int (*)(const ba_params*, uint32_t, uint64_t, bool, bool);
+using KingDeviceEntry = int (*)(ba_ctx*, const ba_params*, uint32_t, uint64_t, const uint32_t*,
+                                const uint8_t*, uint64_t*, uint8_t*, uint8_t*, uint64_t*, void*);
+
+static int king_host_run(KingValidate check, KingDeviceEntry device_entry, const char* chunk_env,
+                         ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
+                         const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
+                         uint8_t* outcome, uint8_t* settled, ba_counters* counters) {
     if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
-    int rc = validate_king(p, policy, batch, faulty != nullptr, order != nullptr);
+    int rc = check(p, policy, batch, faulty != nullptr, order != nullptr);
     if (rc != BA_OK) return rc;
     if (counters) memset(counters, 0, sizeof *counters);
     if (batch == 0) return BA_OK;
@@ -1281,7 +1288,7 @@ extern "C" int ba_king_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t poli
     HIP_TRY(ctx_order(ctx, st));  // the io buffers follow the ctx's last call
     const bool need_f = p->faulty_mode == BA_FAULTY_GIVEN, need_o = p->order_mode == BA_ORDER_GIVEN;
     uint64_t chunk = kKingHostChunk;
-    if (const char* e = getenv("BA_KING_HOST_CHUNK")) {  // tests: chunk a small batch (multiple of 64)
+    if (const char* e = getenv(chunk_env)) {  // tests: chunk a small batch (multiple of 64)
         const uint64_t c = strtoull(e, nullptr, 0) & ~63ull;
         if (c) chunk = c;
     }
@@ -1302,12 +1309,10 @@ extern "C" int ba_king_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t poli
         if (need_f)
             HIP_TRY(hipMemcpyAsync(ctx->io_faulty.p, faulty + t0, nt * 4, hipMemcpyHostToDevice, st));
         if (need_o) HIP_TRY(hipMemcpyAsync(ctx->io_order.p, order + t0, nt, hipMemcpyHostToDevice, st));
-        rc = ba_king_run_trials_device(ctx, &q, policy, nt,
-                                       need_f ? (const uint32_t*)ctx->io_faulty.p : nullptr,
-                                       need_o ? (const uint8_t*)ctx->io_order.p : nullptr,
-                                       decisions ? (uint64_t*)ctx->io_dec.p : nullptr,
-                                       outcome ? d_out : nullptr, settled ? d_set : nullptr,
-                                       (uint64_t*)ctx->io_cnt.p, st);
+        rc = device_entry(ctx, &q, policy, nt, need_f ? (const uint32_t*)ctx->io_faulty.p : nullptr,
+                          need_o ? (const uint8_t*)ctx->io_order.p : nullptr,
+                          decisions ? (uint64_t*)ctx->io_dec.p : nullptr, outcome ? d_out : nullptr,
+                          settled ? d_set : nullptr, (uint64_t*)ctx->io_cnt.p, st);
         if (rc != BA_OK) return rc;
         if (decisions)
             HIP_TRY(hipMemcpyAsync(decisions + t0, ctx->io_dec.p, nt * 8, hipMemcpyDeviceToHost, st));
@@ -1319,6 +1324,68 @@ extern "C" int ba_king_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t poli
     HIP_TRY(hipStreamSynchronize(st));
     if (counters) memcpy(counters->v, h_cnt, sizeof h_cnt);
     return BA_OK;
+}
+
+extern "C" int ba_king_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
+                                  const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
+                                  uint8_t* outcome, uint8_t* settled, ba_counters* counters) {
+    return king_host_run(validate_king, ba_king_run_trials_device, "BA_KING_HOST_CHUNK", ctx, p, policy,
+                         batch, faulty, order, decisions, outcome, settled, counters);
+}
+
+// ---------------------------------------------------------------------------
+// KING3, the three-round King algorithm (docs/SEMANTICS.md §10; ba_king3.hip)
+// ---------------------------------------------------------------------------
+// P = min(m, n-1) + 1 <= n, m <= 10 at this entry (32 > 3 * 10)
+extern "C" uint32_t ba_king3_phases(uint32_t n, uint32_t m) {
+    if (n < 1 || n > BA_MAX_GENERALS || m > kKing3MaxM) return 0;
+    return (m < n - 1 ? m : n - 1) + 1;
+}
+
+// ceil(n/2) calls serve one sender's n recipients: the commander's send, and per
+// phase n senders' values, n senders' proposals and the king's
+extern "C" uint64_t ba_king3_coin_calls(uint32_t n, uint32_t m) {
+    const uint64_t P = ba_king3_phases(n, m);
+    if (P == 0) return 0;
+    return (uint64_t)((n + 1) / 2) * (1 + P * (2 * n + 1));
+}
+
+static int validate_king3(const ba_params* p, uint32_t policy, uint64_t batch, bool has_faulty,
+                          bool has_order) {
+    if (!p) return fail(BA_EINVAL, "params is NULL");
+    if (p->lie_mode == BA_LIE_TABLE)
+        return fail(BA_ENOTSUP, "KING3 draws its coins from Philox only (no table mode)");
+    int rc = validate(p, batch, has_faulty, has_order, false, kKing3MaxM);
+    if (rc != BA_OK) return rc;
+    if (p->engine != BA_ENGINE_AUTO)
+        return fail(BA_EINVAL, "engine=%u: KING3 has one engine (BA_ENGINE_AUTO)", p->engine);
+    if (policy > BA_KING_SPLIT) return fail(BA_EINVAL, "policy=%u", policy);
+    return BA_OK;
+}
+
+extern "C" int ba_king3_run_trials_device(ba_ctx* ctx, const ba_params* p, uint32_t policy,
+                                          uint64_t batch, const uint32_t* d_faulty,
+                                          const uint8_t* d_order, uint64_t* d_decisions,
+                                          uint8_t* d_outcome, uint8_t* d_settled,
+                                          uint64_t* d_counters, void* stream) {
+    return ordered(ctx, stream, [&] {
+        int rc = validate_king3(p, policy, batch, d_faulty != nullptr, d_order != nullptr);
+        if (rc != BA_OK) return rc;
+        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
+        if (batch == 0) return BA_OK;
+        // make_args sizes nothing by m: a.me = min(m, n - 2) is a number k_king3 never reads
+        const RunArgs a = make_args(ctx, p, batch, d_faulty, d_order, nullptr, nullptr, d_decisions,
+                                    d_outcome, d_counters, stream);
+        HIP_TRY(launch_king3(a, policy, ba_king3_phases(p->n, p->m), d_settled));
+        return BA_OK;
+    });
+}
+
+extern "C" int ba_king3_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
+                                   const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
+                                   uint8_t* outcome, uint8_t* settled, ba_counters* counters) {
+    return king_host_run(validate_king3, ba_king3_run_trials_device, "BA_KING3_HOST_CHUNK", ctx, p,
+                         policy, batch, faulty, order, decisions, outcome, settled, counters);
 }
 
 // ---------------------------------------------------------------------------

@@ -218,4 +218,10 @@ hipError_t launch_enum(const RunArgs& a, const EnumCase& g, const uint8_t* d_map
 // policy: BA_KING_*.  settled optional.
 hipError_t launch_king(const RunArgs& a, uint32_t policy, uint32_t phases, uint8_t* settled);
 
+// The three-round King algorithm (ba_king3.hip, docs/SEMANTICS.md §10): the same
+// arguments; a.m (up to kKing3MaxM) is the parameter m of the thresholds n - m and
+// m + 1 and of the in-bound rule n > 3m.
+constexpr uint32_t kKing3MaxM = 10;
+hipError_t launch_king3(const RunArgs& a, uint32_t policy, uint32_t phases, uint8_t* settled);
+
 }  // namespace ba

@@ -23,13 +23,14 @@
 //               consecutive: no bank conflict), read back by lane l ^ 32
 //   kmaj, agr   the king's majority plane; the loyal attack / retreat holders of `settled`
 // The DS instructions of one wave execute in issue order, so between the steps
-// only the compiler has to be held (wave_sync).
+// only the compiler has to be held (king_wave_sync; the wave helpers are
+// ba_king_common.hpp's, shared with k_king3).
 //
 // Three wave-uniform shortcuts, all invisible in the results: a group of calls
 // none of whose senders is faulty in a trial of the word is not drawn (a loyal
 // sender's coin is never read), BA_KING_SPLIT draws nothing at all, and a king
 // loyal throughout the word draws no king coins.
-#include "ba_engine.hpp"
+#include "ba_king_common.hpp"
 
 namespace ba {
 
@@ -44,64 +45,6 @@ struct KingWave {
     uint64_t kmaj;
     uint64_t agr[2];
 };
-
-// orders this wave's LDS accesses for the compiler (no instruction: one wave's
-// DS operations complete in order)
-__device__ __forceinline__ void king_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void king_lds_or(uint64_t* p, uint64_t v) {
-    (void)__hip_atomic_fetch_or((unsigned long long*)p, (unsigned long long)v, __ATOMIC_RELAXED,
-                                __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// the value of lane ^ 1 (DPP quad_perm [1,0,3,2])
-__device__ __forceinline__ uint64_t swap_neighbour(uint64_t v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)v, 0xB1, 0xF, 0xF, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(v >> 32), 0xB1, 0xF, 0xF, false);
-    return (uint64_t)hi << 32 | lo;
-}
-
-// Wave totals of one word's run counters added into `mine` (lane c holds
-// counter c): flags by ballot + popcount, the small integers bit-sliced
-// (faulty_total up to 32 per trial: six planes).
-__device__ __forceinline__ void king_counts_add(bool live, const TrialResult& r, uint32_t lane,
-                                                uint64_t& mine) {
-    const uint32_t o = r.out, q = o & 3;
-    const bool agree = (o >> 2) & 1, appl = (o >> 3) & 1, valid = (o >> 4) & 1, inb = (o >> 5) & 1;
-    uint32_t c[C_NUM];
-    c[C_TRIALS] = __popcll(__ballot(live));
-    c[C_AGREE] = __popcll(__ballot(live && agree));
-    c[C_VAPPL] = __popcll(__ballot(live && appl));
-    c[C_VALID] = __popcll(__ballot(live && valid));
-    c[C_QR] = __popcll(__ballot(live && q == 0));
-    c[C_QA] = __popcll(__ballot(live && q == 1));
-    c[C_QU] = __popcll(__ballot(live && q == 2));
-    c[C_INB] = __popcll(__ballot(live && inb));
-    c[C_VIOL] = __popcll(__ballot(live && inb && (!agree || (appl && !valid))));
-    c[C_UNDEF] = c[C_FTOT] = c[C_ATT] = 0;
-#pragma unroll
-    for (int b = 0; b < 6; ++b) {
-        c[C_FTOT] += (uint32_t)__popcll(__ballot(live && ((r.nf >> b) & 1u))) << b;
-        c[C_ATT] += (uint32_t)__popcll(__ballot(live && ((r.nA >> b) & 1u))) << b;
-    }
-#pragma unroll
-    for (int i = 0; i < C_NUM; ++i)
-        if (lane == (uint32_t)i) mine += c[i];
-}
-
-// The coin words sender j shows this lane's recipient i, for the lane's own call
-// (pair = 16 j + i / 2): `keep` is i's half, `give` that of recipient i ^ 1.
-struct KingCoin {
-    uint64_t keep, give;
-};
-__device__ __forceinline__ KingCoin king_halves(const P4& o, uint32_t odd) {
-    const uint64_t even_r = (uint64_t)o.y << 32 | o.x, odd_r = (uint64_t)o.w << 32 | o.z;
-    return KingCoin{odd ? odd_r : even_r, odd ? even_r : odd_r};
-}
 
 // One group of G sender pairs of an exchange round: this lane's pairs are
 // u = v0 + 2 g + s.  Adds the 2 G votes general i is shown into its tally.
@@ -170,36 +113,6 @@ __device__ __forceinline__ void king_exchange_group(const KingWave& s, uint32_t 
     static_assert(kKingPartPlanes == 5, "a slice's tally: up to 16 votes");
 }
 
-// The coin word a faulty sender j shows recipient i in round q (every lane draws
-// its own copy of the pair's call: one call deep, whatever n).
-template <bool COIN>
-__device__ __forceinline__ uint64_t king_one_coin(uint32_t j, uint32_t i, uint32_t q, uint64_t gw,
-                                                  uint64_t seed) {
-    if constexpr (COIN) {
-        const P4 o = philox10(P4{16u * j + (i >> 1), kKingTag + q, (uint32_t)gw, (uint32_t)(gw >> 32)},
-                              (uint32_t)seed, (uint32_t)(seed >> 32));
-        return king_halves(o, i & 1u).keep;
-    } else {
-        return (i & 1u) ? ~0ull : 0ull;
-    }
-}
-
-// Bit `lane` of: do the loyal generals hold one common preference?  (lanes i < n
-// of slice 0 contribute; `pref` and `myF` are general i's planes)
-__device__ __forceinline__ bool king_agree(KingWave& s, uint32_t lane, uint32_t n, uint64_t pref,
-                                           uint64_t myF) {
-    king_wave_sync();
-    if (lane == 0) s.agr[0] = s.agr[1] = 0;
-    king_wave_sync();
-    if (lane < n) {
-        king_lds_or(&s.agr[1], pref & ~myF);
-        king_lds_or(&s.agr[0], ~pref & ~myF);
-    }
-    king_wave_sync();
-    const uint64_t split = s.agr[0] & s.agr[1];
-    return ((split >> lane) & 1ull) == 0;
-}
-
 template <bool GEN, bool COIN>
 __global__ __launch_bounds__(kKingThreads) void k_king(uint32_t n, uint32_t m, uint32_t phases,
                                                        uint64_t seed, GenSpec gen,
@@ -244,7 +157,7 @@ __global__ __launch_bounds__(kKingThreads) void k_king(uint32_t n, uint32_t m, u
         // round 0: the commander sends
         uint64_t pref = OB;
         if (F0 != 0) {
-            const uint64_t c = king_one_coin<COIN>(0, i, 0, gw, seed);
+            const uint64_t c = king_one_coin<COIN, kKingTag>(0, i, 0, gw, seed);
             if (i != 0) pref = (OB & ~F0) | (F0 & c);
         }
         if (i >= n) pref = 0;
@@ -290,7 +203,7 @@ __global__ __launch_bounds__(kKingThreads) void k_king(uint32_t n, uint32_t m, u
             const uint64_t kmaj = s.kmaj, Fk = s.F[k];
             uint64_t km = kmaj;
             if (__ballot(Fk != 0) != 0) {
-                const uint64_t c = king_one_coin<COIN>(k, i, 2 * p, gw, seed);
+                const uint64_t c = king_one_coin<COIN, kKingTag>(k, i, 2 * p, gw, seed);
                 if (i != k) km = (kmaj & ~Fk) | (Fk & c);
             }
             pref = hi | (~lo & km);

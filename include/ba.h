@@ -400,6 +400,52 @@ uint64_t ba_king_coin_calls(uint32_t n, uint32_t m);   /* host only */
 /* P = min(m, n-1) + 1; 0 for n outside 1..32 or m > 8. */
 uint32_t ba_king_phases(uint32_t n, uint32_t m);       /* host only */
 
+/* ---- KING3: the three-round King algorithm, unsigned, polynomial, n > 3m -------
+ * Berman, Garay and Perry's second algorithm (docs/SEMANTICS.md §10; no ba.py
+ * analogue): Phase King's setting, participants, faulty stance, adversaries and
+ * outputs, but three rounds per phase, about 2n^2 + n messages, and agreement
+ * whenever n > 3m, the optimal resilience that OM(m) pays for with its relay tree.
+ *   round 0      as Phase King's;
+ *   phase p      p = 1..P, P = ba_king3_phases(n, m) = min(m, n-1) + 1, king = general
+ *                p-1.  All thresholds use the parameter m and compare signed integers
+ *                (n - m <= 0 always holds).
+ *                Value: everyone sends its preference; general i counts the attack
+ *                votes c1 of all n generals (its own true value included), c0 = n - c1,
+ *                and will propose retreat if c0 >= n-m, else attack if c1 >= n-m, else
+ *                nothing.  Propose: everyone shows its proposal (a faulty sender always
+ *                proposes); i counts d0 and d1, x = retreat if d0 > m, else attack if
+ *                d1 > m, else its preference; sure = [d_x >= n-m].  King: the king
+ *                sends its x; i keeps x if sure, else takes the king's value (the king
+ *                its own);
+ *   decision     as Phase King's.
+ * A faulty sender j shows recipient r, in place of the truth, under
+ *   BA_KING_COIN   the coin c(q, 32 j + r) = coin(192 + q, 32 j + r), q = 0 the
+ *                  commander's send, 3p-2 / 3p-1 / 3p phase p's rounds;
+ *   BA_KING_SPLIT  r & 1 in every round (no coin is drawn).
+ * Neither is the worst case: rates beyond the bound are rates against these two.
+ * In-bound means |F| <= m and n > 3m.  p->m <= 10 at these entries (32 > 3 * 10; every
+ * other entry keeps BA_MAX_DEPTH), else BA_EINVAL; p->lie_mode must be BA_LIE_PHILOX
+ * (TABLE: BA_ENOTSUP), p->engine BA_ENGINE_AUTO, policy <= BA_KING_SPLIT (else
+ * BA_EINVAL); every faulty/order mode, first_trial and seed as in ba_run_trials, and
+ * the synthetic inputs are ba_run_trials' own.  decisions / outcome / counters /
+ * settled: as ba_king_run_trials. */
+int ba_king3_run_trials(struct ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
+                        const uint32_t* faulty_mask, const uint8_t* order, uint64_t* decisions,
+                        uint8_t* outcome, uint8_t* settled,
+                        ba_counters* counters);            /* counters overwritten */
+/* The same rounds on device buffers, enqueued on `stream` in the ctx's call order
+ * (NULL = HIP's null stream). */
+int ba_king3_run_trials_device(struct ba_ctx* ctx, const ba_params* p, uint32_t policy,
+                               uint64_t batch, const uint32_t* d_faulty_mask,
+                               const uint8_t* d_order, uint64_t* d_decisions, uint8_t* d_outcome,
+                               uint8_t* d_settled, uint64_t* d_counters,
+                               void* stream);              /* accumulated, async */
+/* ceil(n/2) (1 + P (2n+1)): Philox calls per 64-trial word when every sender is faulty
+ * somewhere in the word.  0 for n outside 1..32 or m > 10. */
+uint64_t ba_king3_coin_calls(uint32_t n, uint32_t m);  /* host only */
+/* P = min(m, n-1) + 1; 0 for n outside 1..32 or m > 10. */
+uint32_t ba_king3_phases(uint32_t n, uint32_t m);      /* host only */
+
 /* ---- one huge instance split by first-hop subtree --------
  * The subtree of first-hop lieutenant j (relay paths starting 0 -> j) needs
  * only L_0[j]; its relay levels and inner majorities are independent of the

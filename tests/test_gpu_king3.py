@@ -1,0 +1,278 @@
+"""GPU tests of the three-round King algorithm (docs/SEMANTICS.md §10): k_king3
+through the C ABI against the message-form reference model (tests/king3_model.py).
+Every comparison is exact: decisions, outcome bytes, settled bytes and all 12 run
+counters."""
+import ctypes
+import functools
+import itertools
+
+import numpy as np
+import pytest
+
+import ba_oracle as O
+import king3_model as K3
+
+pytestmark = pytest.mark.gpu
+
+# (1,0), (2,1): degenerate; (3,5): m > n-1, thresholds <= 0; (4,1): the smallest
+# n > 3m; (6,2): n = 3m; (5,3): n <= 2m, both proposals possible; (13,4): odd n, a
+# sender pair with one sender; (17,5): a second group of sender pairs; (31,10),
+# (32,10): the last lanes, eleven phases, q = 33, thresholds 22 and 11; (32,0): one
+# phase, threshold n - m = 32, the six-plane tally's top value
+SHAPES = [(1, 0), (2, 1), (3, 5), (4, 1), (6, 2), (5, 3), (7, 2), (10, 3), (13, 4), (17, 5),
+          (31, 10), (32, 10), (32, 0)]
+SEEDS = [0xBA5EED, 0x5157ED0123456789]
+POLICIES = [K3.KING_COIN, K3.KING_SPLIT]
+B = 229  # three full words and a partial one
+
+
+def arrays(ref):
+    dec, out, stl, cnt = ref
+    return np.array(dec, np.uint64), np.array(out, np.uint8), np.array(stl, np.uint8), cnt
+
+
+@functools.lru_cache(maxsize=None)
+def model(n, m, policy, batch, seed, faulty_mode, f, order_mode, first_trial=0):
+    """Reference results of a run that draws its own inputs (computed once, shared)."""
+    return arrays(K3.run(n, m, policy, seed=seed, faulty_mode=faulty_mode, f=f, order_mode=order_mode,
+                         first_trial=first_trial, batch=batch))
+
+
+def same(a, b, what):
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.shape == b.shape, f"{what}: shape {a.shape} != {b.shape}"
+    if not np.array_equal(a, b):
+        idx = np.nonzero(a != b)[0]
+        raise AssertionError(f"{what}: {len(idx)} mismatches, first at {idx[:5].tolist()}: "
+                             f"got {a[idx[:5]].tolist()} want {b[idx[:5]].tolist()}")
+
+
+def check(res, ref, what):
+    dec, out, stl, cnt = ref
+    same(res.decisions, dec, f"{what} decisions")
+    same(res.outcome, out, f"{what} outcome")
+    same(res.settled, stl, f"{what} settled")
+    assert len(cnt) == 12
+    assert {k: res.counters[k] for k in cnt} == cnt, what
+
+
+@pytest.mark.parametrize("policy", POLICIES)
+@pytest.mark.parametrize("seed", SEEDS)
+@pytest.mark.parametrize("n,m", SHAPES)
+def test_shapes_bit_exact(engine, n, m, seed, policy):
+    from ba_amd import lib as L
+    res = engine.run_king3(n, m, B, policy, seed=seed, faulty_mode=L.FAULTY_RANDOM, f=n,
+                           order_mode=L.ORDER_RANDOM, want_settled=True)
+    check(res, model(n, m, policy, B, seed, O.FAULTY_RANDOM, n, O.ORDER_RANDOM), f"n={n} m={m}")
+    assert res.counters["undefined_decisions"] == 0
+
+
+@pytest.mark.parametrize("policy", POLICIES)
+@pytest.mark.parametrize("first", [0, 320, 1 << 38])
+def test_first_trial(engine, first, policy):
+    from ba_amd import lib as L
+    res = engine.run_king3(10, 3, B, policy, seed=SEEDS[0], faulty_mode=L.FAULTY_RANDOM, f=10,
+                           order_mode=L.ORDER_RANDOM, first_trial=first, want_settled=True)
+    check(res, model(10, 3, policy, B, SEEDS[0], O.FAULTY_RANDOM, 10, O.ORDER_RANDOM, first),
+          f"first={first}")
+
+
+@pytest.mark.parametrize("policy", POLICIES)
+@pytest.mark.parametrize("n,m", [(4, 1), (10, 3), (32, 10)])
+def test_given_inputs(engine, n, m, policy):
+    """No traitor, every general faulty, a faulty commander only, mask bits at and
+    above n (ignored), and every order code, BA_OTHER included."""
+    full = (1 << n) - 1
+    high = (0xFFFFFFFF & ~full) if n < 32 else 0
+    masks = [0, full, 1, high, high | 1, high | full, 0b110 & full, full & ~1]
+    rows = [(fm, oc) for fm in masks for oc in (0, 1, 2)]
+    rows = rows * 4  # 96 trials: two words, the coins differ per trial
+    fm = np.array([r[0] for r in rows], np.uint32)
+    oc = np.array([r[1] for r in rows], np.uint8)
+    res = engine.run_king3(n, m, len(rows), policy, seed=99, faulty=fm, order=oc, first_trial=128,
+                           want_settled=True)
+    ref = K3.run(n, m, policy, seed=99, faulty=fm.tolist(), order=oc.tolist(), first_trial=128,
+                 batch=len(rows))
+    check(res, arrays(ref), f"given n={n} m={m}")
+    # a loyal commander and |F| <= m (all three shapes have n > 3m): every loyal
+    # lieutenant decides the order, and the loyal generals agree from round 0 on
+    assert n > 3 * m
+    lts = (1 << (2 * (n - 1))) - 1
+    seen = 0
+    for i, (f_, o_) in enumerate(rows):
+        f_ &= full
+        if not f_ & 1 and bin(f_).count("1") <= m:
+            loyal = sum(3 << (2 * (r - 1)) for r in range(1, n) if not (f_ >> r) & 1)
+            want = (0x5555555555555555 if o_ == 1 else 0) & lts
+            assert int(res.decisions[i]) & loyal == want & loyal, (i, f_, o_)
+            assert int(res.settled[i]) == 0, (i, f_, o_)
+            seen += 1
+    assert seen >= 24
+
+
+def test_sharding_and_device_accumulation(engine):
+    import torch
+    from ba_amd import lib as L
+    kw = dict(seed=SEEDS[1], faulty_mode=L.FAULTY_RANDOM, f=10, order_mode=L.ORDER_RANDOM)
+    for policy in POLICIES:
+        whole = engine.run_king3(10, 3, 256, policy, want_settled=True, **kw)
+        a = engine.run_king3(10, 3, 128, policy, want_settled=True, **kw)
+        b = engine.run_king3(10, 3, 128, policy, first_trial=128, want_settled=True, **kw)
+        same(np.concatenate([a.decisions, b.decisions]), whole.decisions, "decisions")
+        same(np.concatenate([a.outcome, b.outcome]), whole.outcome, "outcome")
+        same(np.concatenate([a.settled, b.settled]), whole.settled, "settled")
+        assert {k: a.counters[k] + b.counters[k] for k in a.counters} == whole.counters
+        check(whole, model(10, 3, policy, 256, SEEDS[1], O.FAULTY_RANDOM, 10, O.ORDER_RANDOM), "whole")
+        # the device entry accumulates into d_counters across calls
+        cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
+        s = torch.cuda.current_stream().cuda_stream
+        for first in (0, 128):
+            engine.run_king3_device(L.make_params(10, 3, first_trial=first, **kw), 128, policy,
+                                    d_counters=cnt.data_ptr(), stream=s)
+        torch.cuda.synchronize()
+        got = dict(zip(L.COUNTER_NAMES, cnt.cpu().tolist()))
+        assert got == whole.counters
+        assert cnt.cpu().tolist()[12:] == [0, 0, 0, 0]
+
+
+def test_host_entry_chunks(engine, monkeypatch):
+    """The host entry's chunk loop (forced to 64): same bits as one chunk."""
+    from ba_amd import lib as L
+    kw = dict(seed=SEEDS[0], faulty_mode=L.FAULTY_RANDOM, f=10, order_mode=L.ORDER_RANDOM)
+    rng = np.random.default_rng(1)
+    fm = rng.integers(0, 1 << 10, B, dtype=np.uint64).astype(np.uint32)
+    oc = rng.choice([0, 1, 2], B).astype(np.uint8)
+    one = engine.run_king3(10, 3, B, K3.KING_COIN, want_settled=True, **kw)
+    one_g = engine.run_king3(10, 3, B, K3.KING_SPLIT, seed=3, faulty=fm, order=oc, want_settled=True)
+    monkeypatch.setenv("BA_KING3_HOST_CHUNK", "64")
+    for ref, res in ((one, engine.run_king3(10, 3, B, K3.KING_COIN, want_settled=True, **kw)),
+                     (one_g, engine.run_king3(10, 3, B, K3.KING_SPLIT, seed=3, faulty=fm, order=oc,
+                                              want_settled=True))):
+        same(res.decisions, ref.decisions, "decisions")
+        same(res.outcome, ref.outcome, "outcome")
+        same(res.settled, ref.settled, "settled")
+        assert res.counters == ref.counters
+    check(one, model(10, 3, K3.KING_COIN, B, SEEDS[0], O.FAULTY_RANDOM, 10, O.ORDER_RANDOM), "one chunk")
+    check(one_g, arrays(K3.run(10, 3, K3.KING_SPLIT, seed=3, faulty=fm.tolist(), order=oc.tolist(),
+                               batch=B)), "one chunk, given")
+
+
+def test_staged_inputs_equal_in_kernel_draws_and_optional_outputs(engine):
+    """ba_gen_inputs_device + GIVEN == drawing in the kernel; the decisions, outcome
+    and settled pointers are each optional, in every combination, and an absent
+    buffer is not touched."""
+    import torch
+    from ba_amd import lib as L
+    n, m = 10, 3
+    kw = dict(seed=SEEDS[0], faulty_mode=L.FAULTY_RANDOM, f=n, order_mode=L.ORDER_RANDOM)
+    ref = model(n, m, K3.KING_COIN, B, SEEDS[0], O.FAULTY_RANDOM, n, O.ORDER_RANDOM)
+    s = torch.cuda.current_stream().cuda_stream
+    fm = torch.zeros(B, dtype=torch.int32, device="cuda")
+    oc = torch.zeros(B, dtype=torch.uint8, device="cuda")
+    engine.gen_inputs_device(L.make_params(n, m, **kw), B, d_faulty=fm.data_ptr(), d_order=oc.data_ptr(),
+                             stream=s)
+    given = L.make_params(n, m, seed=SEEDS[0])
+    drawn = L.make_params(n, m, **kw)
+    for p, ins in ((given, dict(d_faulty=fm.data_ptr(), d_order=oc.data_ptr())), (drawn, {})):
+        for wd, wo, ws in itertools.product((False, True), repeat=3):
+            dec = torch.full((B,), -1, dtype=torch.int64, device="cuda")
+            out = torch.full((B,), 254, dtype=torch.uint8, device="cuda")
+            stl = torch.full((B,), 254, dtype=torch.uint8, device="cuda")
+            cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
+            engine.run_king3_device(p, B, K3.KING_COIN, d_decisions=dec.data_ptr() if wd else 0,
+                                    d_outcome=out.data_ptr() if wo else 0,
+                                    d_settled=stl.data_ptr() if ws else 0, d_counters=cnt.data_ptr(),
+                                    stream=s, **ins)
+            torch.cuda.synchronize()
+            what = f"given={p is given} dec={wd} out={wo} settled={ws}"
+            same(dec.cpu().numpy().view(np.uint64), ref[0] if wd else np.full(B, 2**64 - 1, np.uint64),
+                 what + " decisions")
+            same(out.cpu().numpy(), ref[1] if wo else np.full(B, 254, np.uint8), what + " outcome")
+            same(stl.cpu().numpy(), ref[2] if ws else np.full(B, 254, np.uint8), what + " settled")
+            assert dict(zip(L.COUNTER_NAMES, cnt.cpu().tolist())) == ref[3], what
+
+
+def test_theory_counters(engine):
+    """The theorem on counters alone, 65,536 trials each: n > 3m and f <= m never
+    break IC1 or IC2 under either policy, at the headline shape (10,3) with three
+    traitors and at (32,10) with ten; f > m can."""
+    from ba_amd import lib as L
+    T = 65536
+    kw = dict(seed=2024, order_mode=L.ORDER_RANDOM, want_decisions=False, want_outcome=False)
+    for policy in POLICIES:
+        for n, m in ((10, 3), (32, 10)):
+            c = engine.run_king3(n, m, T, policy, faulty_mode=L.FAULTY_EXACT, f=m, **kw).counters
+            assert c["trials"] == T and c["in_bound"] == T
+            assert c["bound_violations"] == 0 and c["agreement"] == T
+            assert c["validity"] == c["validity_applicable"]
+            assert c["undefined_decisions"] == 0 and c["faulty_total"] == m * T
+    c = engine.run_king3(7, 2, T, K3.KING_SPLIT, faulty_mode=L.FAULTY_EXACT, f=3, **kw).counters
+    assert c["trials"] == T and c["in_bound"] == 0 and c["bound_violations"] == 0
+    assert c["agreement"] < T
+    assert c["undefined_decisions"] == 0 and c["faulty_total"] == 3 * T
+
+
+def test_errors(engine):
+    from ba_amd import lib as L
+    kw = dict(faulty_mode=L.FAULTY_EXACT, f=0, order_mode=L.ORDER_CONST)
+
+    def code(**over):
+        a = dict(n=4, m=1, batch=64, policy=K3.KING_COIN)
+        a.update(kw)
+        a.update(over)
+        with pytest.raises(L.BAError) as e:
+            engine.run_king3(a.pop("n"), a.pop("m"), a.pop("batch"), a.pop("policy"), **a)
+        return e.value.code
+
+    assert code(lie_mode=L.LIE_TABLE) == L.ENOTSUP
+    assert code(n=0) == L.EINVAL
+    assert code(n=33) == L.EINVAL
+    assert code(n=32, m=11) == L.EINVAL
+    assert engine.run_king3(32, 10, 64, **kw).counters["trials"] == 64  # m = 10 is accepted
+    assert code(policy=2) == L.EINVAL
+    assert code(first_trial=32) == L.EINVAL
+    assert code(faulty_mode=L.FAULTY_GIVEN) == L.EINVAL  # no faulty_mask
+    assert code(order_mode=L.ORDER_GIVEN) == L.EINVAL    # no order
+    for eng in (L.ENGINE_FUSED, L.ENGINE_LEVELS):
+        assert code(engine=eng) == L.EINVAL
+        assert b"engine" in engine.lib.ba_last_error()
+    # the trial index may not wrap: the last trial is at most 2^64 - 1
+    with pytest.raises(L.BAError) as e:
+        engine.run_king3(4, 1, 65, first_trial=2**64 - 64, **kw)
+    assert e.value.code == L.EINVAL and "first_trial" in str(e.value)
+    kr = dict(seed=5, faulty_mode=L.FAULTY_RANDOM, f=4, order_mode=L.ORDER_RANDOM)
+    top = engine.run_king3(4, 1, 64, first_trial=2**64 - 64, want_settled=True, **kr)  # ends at 2^64
+    check(top, arrays(K3.run(4, 1, first_trial=2**64 - 64, batch=64, **kr)), "top")
+    # batch = 0: BA_OK with zero counters
+    res = engine.run_king3(4, 1, 0, **kw)
+    assert all(v == 0 for v in res.counters.values())
+    # NULL params are an error, not a crash
+    cnt = L.Counters()
+    assert engine.lib.ba_king3_run_trials(engine.handle, None, 0, 64, None, None, None, None, None,
+                                          ctypes.byref(cnt)) == L.EINVAL
+    # the ctx still works
+    assert engine.run_king3(4, 1, 64, **kw).counters["trials"] == 64
+    # every other entry keeps its limit m <= 8
+    with pytest.raises(L.BAError) as e:
+        engine.run_king(32, 9, 64, **kw)
+    assert e.value.code == L.EINVAL
+    with pytest.raises(L.BAError) as e:
+        engine.run(10, 9, 64, **kw)
+    assert e.value.code == L.EINVAL
+
+
+def test_bench_size_equals_sum_of_sixteen(engine):
+    """1,048,576 trials at (10, 3) in one call == sixteen 65,536-trial calls:
+    the persistent word loop and the counter sink at bench size."""
+    from ba_amd import lib as L
+    kw = dict(seed=0xBA5EED, faulty_mode=L.FAULTY_RANDOM, f=3, order_mode=L.ORDER_RANDOM,
+              want_decisions=False, want_outcome=False)
+    T, Kc = 1 << 20, 16
+    whole = engine.run_king3(10, 3, T, K3.KING_COIN, **kw).counters
+    tot = dict.fromkeys(whole, 0)
+    for i in range(Kc):
+        c = engine.run_king3(10, 3, T // Kc, K3.KING_COIN, first_trial=i * (T // Kc), **kw).counters
+        for k in tot:
+            tot[k] += c[k]
+    assert whole == tot
+    assert whole["trials"] == T and whole["in_bound"] == T and whole["bound_violations"] == 0
