@@ -788,6 +788,27 @@ def decode_strategy(n: int, m: int, faulty_mask: int, S: int) -> dict:
     return {path_of_rank(n, k, x): (S >> i) & 1 for i, (k, x) in enumerate(enum_slots(n, m, faulty_mask))}
 
 
+def encode_strategy(n: int, m: int, faulty_mask: int, values) -> int:
+    """The strategy index S of `{relay path: value}`, the inverse of decode_strategy:
+    `values` gives 0 / 1 for exactly the free slots of the case (docs/SEMANTICS.md §8).
+    A missing path, a path that is not a free slot and a value other than 0 / 1 raise
+    ValueError.  `run_enum(n, m, faulty_mask, order, first=S & ~63, count=...)` then
+    re-runs a hand-written strategy as element S & 63."""
+    given = {tuple(p): v for p, v in dict(values).items()}
+    paths = [path_of_rank(n, k, x) for k, x in enum_slots(n, m, faulty_mask)]
+    missing = [p for p in paths if p not in given]
+    extra = sorted(set(given) - set(paths))
+    if missing or extra:
+        raise ValueError(f"strategy of (n={n}, m={m}, F={faulty_mask:#b}) has {len(paths)} free slots: "
+                         f"missing {missing[:4]}, not free {extra[:4]}")
+    S = 0
+    for i, p in enumerate(paths):
+        if given[p] not in (0, 1):
+            raise ValueError(f"value of path {p} is {given[p]!r}, not 0 or 1")
+        S |= int(given[p]) << i
+    return S
+
+
 def vote_slots(n: int, m: int, j_begin: int, j_end: int) -> int:
     """Vote slots of first-hop subtrees [j_begin, j_end) per 64-trial word."""
     return int(load().ba_vote_slots(n, m, j_begin, j_end))
