@@ -459,7 +459,8 @@ class Engine:
         (ba_enum_run_device); counters accumulated, the witness (uint64, set to NO_WITNESS
         by the caller) min-accumulated.  The kernels are queued asynchronously, but the call
         first copies the case's slot map from host memory and returns only after the
-        stream's earlier work has drained (include/ba.h)."""
+        stream's earlier work has drained (include/ba.h).  On a stream that is capturing a
+        graph it raises BAError(ENOTSUP) and queues nothing."""
         _check(self.lib, self.lib.ba_enum_run_device(
             self.handle, ctypes.byref(params), faulty_mask & 0xFFFFFFFF, order, count,
             d_decisions or None, d_outcome or None, d_counters or None, d_witness or None,
@@ -472,7 +473,8 @@ class Engine:
         return h.value or 0
 
     def profile(self, on: bool):
-        """Enable/disable per-kernel HIP-event timing (clears the totals)."""
+        """Enable/disable per-kernel HIP-event timing (clears the totals).  Launches on
+        a stream that is capturing a graph are not timed."""
         _check(self.lib, self.lib.ba_profile_enable(self.handle, int(on)))
 
     def profile_read(self) -> dict:

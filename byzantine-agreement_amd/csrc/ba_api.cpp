@@ -295,11 +295,13 @@ hipEvent_t Prof::take() {
     (void)hipEventCreateWithFlags(&e, hipEventReleaseToDevice);  // timing only: no system-scope fence
     return e;
 }
-void Prof::begin(const char* name, hipStream_t s) {
+bool Prof::begin(const char* name, hipStream_t s) {
+    if (stream_capturing(s)) return false;  // launches of a capture are not bracketed (ba.h)
     stream = s;
     Rec r{name, take(), take()};
     (void)hipEventRecord(r.a, s);
     pending.push_back(r);
+    return true;
 }
 void Prof::end() { (void)hipEventRecord(pending.back().b, stream); }
 }  // namespace ba
@@ -1549,6 +1551,12 @@ extern "C" int ba_enum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t faul
                                   uint32_t order, uint64_t batch, uint64_t* d_decisions,
                                   uint8_t* d_outcome, uint64_t* d_counters, uint64_t* d_witness,
                                   void* stream) {
+    // refused before anything is queued on the stream: the map copy (enum_upload)
+    // would become a graph node whose source, the plan's host vector, is gone
+    // when a replay reads it
+    if (ctx && stream_capturing((hipStream_t)stream))
+        return fail(BA_ENOTSUP, "ba_enum_run_device on a stream that is capturing a graph: its slot "
+                    "map is copied from host memory that does not outlive the call");
     return ordered(ctx, stream, [&] {
         EnumPlan pl;
         int rc = validate_enum(p, faulty_mask, order, batch, pl);

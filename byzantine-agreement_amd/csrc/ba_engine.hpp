@@ -22,7 +22,10 @@ struct Prof {
     std::vector<hipEvent_t> pool;
     hipStream_t stream = nullptr;
     hipEvent_t take();
-    void begin(const char* name, hipStream_t s);
+    // false (nothing recorded, no end() due): s is capturing a graph -- an event
+    // recorded there becomes a graph node and is never recorded eagerly, so
+    // ba_profile_read could not synchronise on it
+    bool begin(const char* name, hipStream_t s);
     void end();
 };
 
@@ -51,11 +54,11 @@ struct RunArgs {
 
 struct ProfScope {  // RAII: times one launch when profiling is on
     Prof* p;
-    ProfScope(Prof* p_, const char* name, hipStream_t s) : p(p_) {
-        if (p && p->on) p->begin(name, s);
-    }
+    bool live;  // begin() recorded: end() is due
+    ProfScope(Prof* p_, const char* name, hipStream_t s)
+        : p(p_), live(p_ && p_->on && p_->begin(name, s)) {}
     ~ProfScope() {
-        if (p && p->on) p->end();
+        if (live) p->end();
     }
 };
 

@@ -325,8 +325,9 @@ uint64_t ba_adv_paths(uint32_t n, uint32_t m);   /* host only */
  * pageable host memory to the device on the call's stream.  The HIP runtime finishes
  * such a copy before it returns, so ba_enum_run_device is NOT fully asynchronous: it
  * returns after the stream's earlier work has drained and the map has landed, with
- * its own launches queued behind.  For the same reason do not capture these entries
- * into a graph.  (ba_enum_run plans the case and copies the map once, whatever the
+ * its own launches queued behind.  For the same reason ba_enum_run_device on a stream
+ * that is capturing a graph is refused with BA_ENOTSUP, before anything is queued on
+ * the stream: the capture stays valid.  (ba_enum_run plans the case and copies the map once, whatever the
  * number of its output chunks.) */
 #define BA_ENUM_MAX_BITS 48
 /* B; host only.  0xFFFFFFFF for n outside 1..32 or m > 8; saturates at 0xFFFFFFFE. */
@@ -603,7 +604,9 @@ int ba_run_instance_split_level_multi(struct ba_ctx* ctx, struct ba_comm* comm,
  * only prints).  When enabled, every kernel the ctx launches is bracketed by
  * HIP events on its launch stream; ba_profile_read syncs those events and
  * returns the index-th kernel's name, launch count and summed milliseconds
- * (BA_EINVAL past the last kernel).  Enabling/disabling clears the totals. */
+ * (BA_EINVAL past the last kernel).  Enabling/disabling clears the totals.
+ * Launches on a stream that is capturing a graph are not bracketed: neither the
+ * capture nor its replays add to the totals. */
 int ba_profile_enable(struct ba_ctx* ctx, int on);
 int ba_profile_read(struct ba_ctx* ctx, int index, char* name, int name_len,
                     uint64_t* launches, double* total_ms);

@@ -413,22 +413,30 @@ OM4_CASES = [(6, 4, 1), (6, 5, 2), (7, 4, 2), (8, 4, 2), (9, 4, 3), (10, 4, 3), 
 @pytest.mark.parametrize("n,m,f", OM4_CASES)
 def test_om4_wave_vs_oracle(monkeypatch, n, m, f):
     """k_om4w (rounds over second-level subtrees, R1 counters per first hop)
-    against the oracle on a ragged batch, with and without the persistent task
-    loop (BA_WAVE_MAX_BLOCKS=1 or 2: one or two blocks take tasks from the ctx's
-    dynamic counter; BA_WAVE_STATIC_TASKS=1: the static stride), random faulty
-    sets and given inputs."""
+    against the oracle on ragged batches, random faulty sets and given inputs (the
+    staged kernel k_om4w<N, true>).  The default grid on 14 words: at most 3 tasks,
+    one per wave, no task loop.  BA_WAVE_MAX_BLOCKS=1 or 2 on 11 W + 1 words: 12 tasks,
+    the last a single partial word, on 4 or 8 waves, so every wave walks the task loop
+    -- tasks from the ctx's dynamic counter, or (BA_WAVE_STATIC_TASKS=1) by the static
+    stride.  wave_shape holds each variant to the path it names."""
     from ba_amd import lib as L
+    from wave_shape import cu_count, om4w_words, wave_shape
     assert L.load().ba_engine_for(n, m) == L.ENGINE_FUSED
-    B = 64 * 13 + 37
-    kw = dict(seed=0x4A11 + n, faulty_mode=L.FAULTY_RANDOM, f=f, order_mode=L.ORDER_RANDOM,
-              first_trial=64 * 55)
-    od, oo, ocnt = oracle_c.run(n, m, B, **kw)
-    rng = np.random.default_rng(n)
-    fm = (rng.integers(0, 1 << n, B, dtype=np.uint64) & rng.integers(0, 1 << n, B, dtype=np.uint64)
-          ).astype(np.uint32)
-    oc = rng.choice([0, 1, 2], B).astype(np.uint8)
-    gd, go, gcnt = oracle_c.run(n, m, B, seed=3, faulty=fm, order=oc)
+    W = om4w_words(n)
+
+    def references(B):
+        kw = dict(seed=0x4A11 + n, faulty_mode=L.FAULTY_RANDOM, f=f, order_mode=L.ORDER_RANDOM,
+                  first_trial=64 * 55)
+        rng = np.random.default_rng(n)
+        fm = (rng.integers(0, 1 << n, B, dtype=np.uint64) & rng.integers(0, 1 << n, B, dtype=np.uint64)
+              ).astype(np.uint32)
+        oc = rng.choice([0, 1, 2], B).astype(np.uint8)
+        return kw, oracle_c.run(n, m, B, **kw), fm, oc, oracle_c.run(n, m, B, seed=3, faulty=fm, order=oc)
+
+    refs = {B: references(B) for B in (64 * 13 + 37, 64 * W * 11 + 37)}
     for cap, stat in ((None, "0"), ("1", "0"), ("2", "0"), ("2", "1")):
+        B = 64 * W * 11 + 37 if cap else 64 * 13 + 37
+        kw, (od, oo, ocnt), fm, oc, (gd, go, gcnt) = refs[B]
         monkeypatch.setenv("BA_WAVE_STATIC_TASKS", stat)
         if cap:
             monkeypatch.setenv("BA_WAVE_MAX_BLOCKS", cap)
@@ -436,6 +444,12 @@ def test_om4_wave_vs_oracle(monkeypatch, n, m, f):
             monkeypatch.delenv("BA_WAVE_MAX_BLOCKS", raising=False)
         e = L.Engine(0)
         try:
+            shape = wave_shape(W, B, cap, cu_count(e))
+            if cap:
+                assert shape.persistent and shape.tasks == 12 and shape.blocks == int(cap), shape
+                assert shape.words == 11 * W + 1  # the last task: one partial word
+            else:
+                assert not shape.persistent and shape.tasks <= 3, shape
             res = e.run(n, m, B, engine=L.ENGINE_FUSED, **kw)
             given = e.run(n, m, B, seed=3, faulty=fm, order=oc, engine=L.ENGINE_FUSED)
         finally:
@@ -614,6 +628,52 @@ def test_two_ctxs_in_flight_equal_one_stream():
                 total[k] += v
         got = dict(zip(L.COUNTER_NAMES, [int(x) for x in cnt.cpu().tolist()]))
         assert {k: got[k] for k in total} == total
+    finally:
+        for e in engs:
+            e.close()
+
+
+def test_two_ctxs_om4w_task_loops_in_flight(monkeypatch):
+    """Two ctxs, each with its own task counter, run k_om4w's dynamic task loop at once:
+    (9, 4) under BA_WAVE_MAX_BLOCKS=2 on 11 W + 1 words is 12 tasks on 8 waves per
+    launch.  Six calls alternate over the two ctxs, each on its own ctx stream; every
+    call's outputs and the summed counters equal the oracle's."""
+    import torch
+    from ba_amd import lib as L
+    from wave_shape import cu_count, om4w_words, wave_shape
+    n, m, K = 9, 4, 6
+    W = om4w_words(n)
+    assert W == 10
+    B = 64 * W * 11 + 37
+    monkeypatch.setenv("BA_WAVE_MAX_BLOCKS", "2")
+    monkeypatch.setenv("BA_WAVE_STATIC_TASKS", "0")
+    monkeypatch.delenv("BA_FUSED_KIND", raising=False)
+    kw = dict(seed=0x4A11, faulty_mode=L.FAULTY_RANDOM, f=4, order_mode=L.ORDER_RANDOM)
+    engs = [L.Engine(0), L.Engine(0)]
+    try:
+        shape = wave_shape(W, B, "2", cu_count(engs[0]))
+        assert shape.persistent and (shape.tasks, shape.blocks) == (12, 2), shape
+        sts = [e.stream() for e in engs]
+        assert sts[0] and sts[1] and sts[0] != sts[1]
+        cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
+        decs = [torch.full((B,), -1, dtype=torch.int64, device="cuda") for _ in range(K)]
+        outs = [torch.full((B,), 254, dtype=torch.uint8, device="cuda") for _ in range(K)]
+        torch.cuda.synchronize()
+        for i in range(K):
+            p = L.make_params(n, m, first_trial=i * 64 * 8000, **kw)
+            engs[i % 2].run_device(p, B, d_decisions=decs[i].data_ptr(), d_outcome=outs[i].data_ptr(),
+                                   d_counters=cnt.data_ptr(), stream=sts[i % 2])
+        torch.cuda.synchronize()
+        total = {k: 0 for k in L.COUNTER_NAMES}
+        for i in range(K):
+            od, oo, oc = oracle_c.run(n, m, B, first_trial=i * 64 * 8000, **kw)
+            same(decs[i].cpu().numpy().view(np.uint64), od, f"decisions call {i}")
+            same(outs[i].cpu().numpy(), oo, f"outcome call {i}")
+            for k, v in oc.items():
+                total[k] += v
+        got = cnt.cpu().tolist()
+        assert dict(zip(L.COUNTER_NAMES, got)) == total
+        assert got[12:] == [0, 0, 0, 0]
     finally:
         for e in engs:
             e.close()

@@ -66,6 +66,51 @@ def test_shapes_bit_exact(engine, n, m, batch, seed, policy):
     check(res, model(n, m, policy, batch, seed), f"n={n} m={m} policy={policy}")
 
 
+def adv_units(n, batch):
+    """Reporting waves of launch_adv (ba_adv.hip): four per block, a block per
+    wpb = min(32, 256 // (n - 1)) trial words (below the per-CU block cap)."""
+    wpb = min(32, 256 // (n - 1))
+    words = (batch + 63) // 64
+    return 4 * ((words + wpb - 1) // wpb)
+
+
+@pytest.mark.parametrize("policy", A.POLICIES)
+@pytest.mark.parametrize("n,m", [(10, 3), (4, 1)])
+def test_sink_path_bit_exact(engine, n, m, policy):
+    """A launch of more than 64 reporting waves adds its counters through the sink's
+    replicas (sink_counters, ba_device.hpp), where the smaller batches above add
+    straight into the caller's.  A k_adv block takes wpb words, so that is 16 wpb + 1
+    words: 17 blocks, 68 waves.  The whole batch against the model through the host
+    entry, then as two device calls accumulating into one d_counters, then twice whole
+    through the device entry (the first launch must leave the replicas zero)."""
+    import torch
+    from ba_amd import lib as L
+    wpb = min(32, 256 // (n - 1))
+    Bs = 64 * 16 * wpb + 37
+    assert adv_units(n, Bs) == 68 and adv_units(n, 64 * 16 * wpb) == 64
+    first = 64 * 9
+    kw = dict(seed=SEEDS[0], f=n, **drawn(L))
+    ref = model(n, m, policy, Bs, SEEDS[0], first)
+    check(engine.run_adv(n, m, Bs, policy, first_trial=first, **kw), ref, f"host n={n} m={m} policy={policy}")
+    s = torch.cuda.current_stream().cuda_stream
+    half = 64 * 8 * wpb
+    for what, calls, times in (("two halves", ((0, half), (half, Bs - half)), 1),
+                               ("whole twice", ((0, Bs), (0, Bs)), 2)):
+        dec = torch.full((Bs,), -1, dtype=torch.int64, device="cuda")
+        out = torch.full((Bs,), 254, dtype=torch.uint8, device="cuda")
+        cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
+        for t0, count in calls:
+            engine.run_adv_device(L.make_params(n, m, first_trial=first + t0, **kw), count, policy,
+                                  d_decisions=dec[t0:].data_ptr(), d_outcome=out[t0:].data_ptr(),
+                                  d_counters=cnt.data_ptr(), stream=s)
+        torch.cuda.synchronize()
+        same(dec.cpu().numpy().view(np.uint64), ref[0], f"{what} decisions")
+        same(out.cpu().numpy(), ref[1], f"{what} outcome")
+        got = cnt.cpu().tolist()
+        assert dict(zip(L.COUNTER_NAMES, got)) == {k: times * v for k, v in ref[2].items()}, what
+        assert got[12:] == [0, 0, 0, 0]
+
+
 @pytest.mark.parametrize("policy", A.POLICIES)
 def test_depth_eight(engine, policy):
     """(10, 8): me = 8, 40,320 chains per receiver, on five given trials."""

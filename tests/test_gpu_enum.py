@@ -106,6 +106,45 @@ def test_theorem_by_exhaustion_one_faulty_lieutenant_of_seven(engine, o):
     assert c["quorum_attack" if o == A else "quorum_retreat"] == T
 
 
+def enum_units(count, want_out):
+    """Reporting waves of launch_enum (ba_enum.hip): a wave per tile of 64 words (4,096
+    strategies); one-wave blocks with per-trial outputs, four-wave blocks without."""
+    tiles = ((count + 63) // 64 + 63) // 64
+    return tiles if want_out else 4 * ((tiles + 3) // 4)
+
+
+def test_sink_path_bit_exact(engine):
+    """The counter sink of k_enum against the model.  A wave takes 4,096 strategies, so
+    a whole space of 16 bits -- one faulty lieutenant of six at m = 2 -- is 16 waves,
+    which add straight into the caller's counters; the sink's replicas need more than
+    64 waves, i.e. more than 2^18 strategies: the first 67 tiles of the 20-bit space
+    of (6, 2) with a faulty commander and lieutenant, with per-trial outputs (67
+    one-wave blocks) and without (17 four-wave blocks, 68 waves), then through the
+    device entry twice (the first launch must leave the replicas zero)."""
+    import torch
+    from ba_amd import lib as L
+    assert E.bits_formula(6, 2, 0b000010) == 16 and enum_units(1 << 16, True) == 16
+    check(full(engine, 6, 2, 0b000010, A), model(6, 2, 0b000010, A), "(6,2) F={1}, whole space")
+    F, count = 0b000011, 67 * 4096
+    assert E.bits_formula(6, 2, F) == 20
+    assert enum_units(count, True) == 67 and enum_units(count, False) == 68
+    ref = model(6, 2, F, A, 0, count)
+    check(full(engine, 6, 2, F, A, first=0, count=count), ref, "67 tiles, outputs")
+    res = engine.run_enum(6, 2, F, A, first=0, count=count)
+    assert res.counters == ref[2] and res.witness == (None if ref[3] == E.NO_WITNESS else ref[3])
+    cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
+    wit = torch.full((1,), -1, dtype=torch.int64, device="cuda")  # 2^64 - 1
+    s = torch.cuda.current_stream().cuda_stream
+    for _ in range(2):
+        engine.run_enum_device(L.make_params(6, 2), F, A, count, d_counters=cnt.data_ptr(),
+                               d_witness=wit.data_ptr(), stream=s)
+    torch.cuda.synchronize()
+    got = cnt.cpu().tolist()
+    assert dict(zip(L.COUNTER_NAMES, got)) == {k: 2 * v for k, v in ref[2].items()}
+    assert got[12:] == [0, 0, 0, 0]
+    assert int(wit.cpu().numpy().view(np.uint64)[0]) == ref[3]
+
+
 def test_symmetry_counters_depend_on_the_class_only(engine):
     for o in (A, R, 2):
         ref = engine.run_enum(5, 2, 0b00110, o).counters

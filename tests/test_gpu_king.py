@@ -64,6 +64,48 @@ def test_shapes_bit_exact(engine, n, m, seed, policy):
     assert res.counters["undefined_decisions"] == 0
 
 
+SINK_B = 64 * 68 + 37  # 69 words: 18 four-wave blocks, 72 reporting waves > the sink's 64 replicas
+
+
+@pytest.mark.parametrize("policy", POLICIES)
+@pytest.mark.parametrize("n,m", [(10, 3), (5, 1)])
+def test_sink_path_bit_exact(engine, n, m, policy):
+    """A launch of more than 64 reporting waves adds its counters through the sink's
+    replicas (sink_counters, ba_device.hpp), where the smaller batches here add
+    straight into the caller's: the whole batch against the model through the host
+    entry, then as two device calls accumulating into one d_counters, then twice
+    whole through the device entry (the first launch must leave the replicas zero).
+    (5, 1) is the smallest shape inside Phase King's bound n > 4m."""
+    import torch
+    from ba_amd import lib as L
+    words = (SINK_B + 63) // 64
+    assert 4 * ((words + 3) // 4) > 64  # launch_king: one unit per wave, four-wave blocks
+    first = 64 * 9
+    kw = dict(seed=SEEDS[0], faulty_mode=L.FAULTY_RANDOM, f=n, order_mode=L.ORDER_RANDOM)
+    ref = model(n, m, policy, SINK_B, SEEDS[0], O.FAULTY_RANDOM, n, O.ORDER_RANDOM, first)
+    check(engine.run_king(n, m, SINK_B, policy, first_trial=first, want_settled=True, **kw), ref,
+          f"host n={n} m={m} policy={policy}")
+    s = torch.cuda.current_stream().cuda_stream
+    half = 64 * 34
+    for what, calls, times in (("two halves", ((0, half), (half, SINK_B - half)), 1),
+                               ("whole twice", ((0, SINK_B), (0, SINK_B)), 2)):
+        dec = torch.full((SINK_B,), -1, dtype=torch.int64, device="cuda")
+        out = torch.full((SINK_B,), 254, dtype=torch.uint8, device="cuda")
+        stl = torch.full((SINK_B,), 254, dtype=torch.uint8, device="cuda")
+        cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
+        for t0, count in calls:
+            engine.run_king_device(L.make_params(n, m, first_trial=first + t0, **kw), count, policy,
+                                   d_decisions=dec[t0:].data_ptr(), d_outcome=out[t0:].data_ptr(),
+                                   d_settled=stl[t0:].data_ptr(), d_counters=cnt.data_ptr(), stream=s)
+        torch.cuda.synchronize()
+        same(dec.cpu().numpy().view(np.uint64), ref[0], f"{what} decisions")
+        same(out.cpu().numpy(), ref[1], f"{what} outcome")
+        same(stl.cpu().numpy(), ref[2], f"{what} settled")
+        got = cnt.cpu().tolist()
+        assert dict(zip(L.COUNTER_NAMES, got)) == {k: times * v for k, v in ref[3].items()}, what
+        assert got[12:] == [0, 0, 0, 0]
+
+
 @pytest.mark.parametrize("policy", POLICIES)
 @pytest.mark.parametrize("first", [0, 64 * 5, 1 << 38])
 def test_first_trial(engine, first, policy):

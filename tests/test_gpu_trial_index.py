@@ -186,15 +186,41 @@ def test_om3w_n10_ends_at_2_64(monkeypatch, cap):
 
 
 # --- WAVE depth 4: k_om4w -----------------------------------------------------------------
+def loop_starts(W):
+    """k_om4w's task loop under BA_WAVE_MAX_BLOCKS=1 (4 waves, 10 tasks): the boundary
+    inside task 8 (a = 9 W - 2 words into the launch) and on its edge (a = 8 W), both
+    streams.  Task 8 is of the third wave-round: a wave reaches it through the loop."""
+    return {"W32loop_in": W32(9 * W - 2), "W32loop_edge": W32(8 * W), "T32loop_in": T32(9 * W - 2),
+            "T32loop_edge": T32(8 * W)}
+
+
 @pytest.mark.parametrize("static", ["0", "1"])
-@pytest.mark.parametrize("start", ["W32in", "W32edge", "T32in", "T32edge", "HI"])
+@pytest.mark.parametrize("start", ["W32in", "W32edge", "T32in", "T32edge", "HI", "W32loop_in", "W32loop_edge",
+                                   "T32loop_in", "T32loop_edge"])
 @pytest.mark.parametrize("n", [6, 13])  # Om4W<N>::W = 64 // (n - 3) = 21 and 6
 def test_om4w(monkeypatch, n, start, static):
-    """The ctx's dynamic task counter and the static stride (BA_WAVE_STATIC_TASKS=1)."""
-    W = 64 // (n - 3)
-    first = task_starts(W)[start]
-    env(monkeypatch, BA_FUSED_KIND=None, BA_WAVE_MAX_BLOCKS=None, BA_WAVE_STATIC_TASKS=static)
-    for prof in check(n, 4, 64 * W * 3 + 11, first, f"n={n} {start} static={static}"):
+    """The default grid (4 tasks on 4 waves: no task loop, whatever `static`), and, the
+    *loop* starts, one block walking 10 tasks (BA_WAVE_MAX_BLOCKS=1) with the carry in a
+    task of the third wave-round: fetched from the ctx's dynamic task counter, or
+    reached by the static stride (BA_WAVE_STATIC_TASKS=1).  The staged run of each is
+    k_om4w<N, true>."""
+    from wave_shape import om4w_words, wave_shape
+    W = om4w_words(n)
+    assert W == 64 // (n - 3)
+    loop = start in loop_starts(W)
+    if loop:
+        first, B, cap = loop_starts(W)[start], 64 * W * 9 + 11, "1"
+        shape = wave_shape(W, B, cap)
+        assert shape.persistent and (shape.tasks, shape.blocks) == (10, 1), shape
+        # the word in which the counter word carries lies in task 8 or later (round 3)
+        carry_word = ((2**38 if start.startswith("W32") else 2**32) - first) // 64
+        assert 8 * W <= carry_word < shape.words and carry_word // W >= 2 * 4 * shape.blocks
+    else:
+        first, B, cap = task_starts(W)[start], 64 * W * 3 + 11, None
+        shape = wave_shape(W, B, cap)
+        assert not shape.persistent and shape.tasks == 4, shape
+    env(monkeypatch, BA_FUSED_KIND=None, BA_WAVE_MAX_BLOCKS=cap, BA_WAVE_STATIC_TASKS=static)
+    for prof in check(n, 4, B, first, f"n={n} {start} static={static}"):
         assert prof.get("k_om4w") == 1 and "k_fused" not in prof, prof
 
 
