@@ -456,17 +456,26 @@ extern "C" void ba_ctx_destroy(ba_ctx* ctx) {
     delete ctx;
 }
 
+// P(L, len) exactly: the geometry helpers report the tree's true size (perm_count
+// saturates at 2^40, which the depth-8 trees over 27 or more generals pass).  In
+// their domain, L <= 31 and len <= 9, the product stays below 2^43.
+static uint64_t perm_exact(uint32_t L, uint32_t len) {
+    uint64_t p = 1;
+    for (uint32_t i = 0; i < len; ++i) p *= i < L ? (uint64_t)(L - i) : 0;
+    return p;
+}
+
 extern "C" uint64_t ba_level_slots(uint32_t n, uint32_t m, uint32_t k) {
-    if (n < 1 || n > BA_MAX_GENERALS) return 0;
+    if (n < 1 || n > BA_MAX_GENERALS || m > BA_MAX_DEPTH) return 0;
     if (k > effective_depth(n, m)) return 0;
-    return perm_count(n - 1, k + 1);
+    return perm_exact(n - 1, k + 1);
 }
 
 extern "C" uint64_t ba_tree_slots(uint32_t n, uint32_t m) {
-    if (n < 1 || n > BA_MAX_GENERALS) return 0;
+    if (n < 1 || n > BA_MAX_GENERALS || m > BA_MAX_DEPTH) return 0;
     uint64_t s = 0;
     const uint32_t me = effective_depth(n, m);
-    for (uint32_t k = 0; k <= me; ++k) s += perm_count(n - 1, k + 1);
+    for (uint32_t k = 0; k <= me; ++k) s += perm_exact(n - 1, k + 1);
     return s;
 }
 

@@ -667,7 +667,8 @@ int ba_mt_table_device(struct ba_ctx* ctx, uint32_t n, uint32_t m, uint64_t batc
                        const uint32_t* d_poll_commander, uint32_t stride, uint32_t* d_table,
                        uint32_t* d_next_word, void* stream);
 
-/* Tree geometry helpers (host only, no device needed). */
+/* Tree geometry helpers (host only, no device needed).  The slot counts are exact;
+ * 0 for n outside 1..32 or m > 8 (ba_level_slots: and for k > min(m, n-2)). */
 uint64_t ba_tree_slots(uint32_t n, uint32_t m);             /* sum_k |L_k|       */
 uint64_t ba_level_slots(uint32_t n, uint32_t m, uint32_t k); /* |L_k|=P(n-1,k+1) */
 int ba_engine_for(uint32_t n, uint32_t m);                  /* engine AUTO picks */

@@ -570,8 +570,17 @@ def test_levels_small_batch_fusions_vs_oracle(monkeypatch, n, m, B):
     BA_NO_LEAF_UP / BA_NO_TAIL = 1): every combination equals the oracle, for
     drawn and given inputs.  (16, 3) and (16, 2) run without leaf fusion (the
     tail then reads R_2 / the leaves L_2); (12, 4) and (9, 5) have relay pairs
-    that straddle two parents in k_relay_top."""
+    that straddle two parents in k_relay_top.  BA_NO_CASCADE=1 keeps every shape on
+    the multi-launch pipeline (at (16, 5) and (10, 3) the one-launch cascade would take
+    the call and the three switches would do nothing), and the kernel profile shows each
+    toggled kernel (the k_input launch, k_leaf_up / k_leaf, k_tail) come and go with its
+    switch, as the dispatch rule restated in om_lattice.py says."""
+    import om_lattice as OL
     from ba_amd import lib as L
+    monkeypatch.setenv("BA_NO_CASCADE", "1")
+    me, words = OL.m_eff(n, m), OL.words_of(B)
+    leaf = OL.leaf_supported(n, me)
+    seen = set()
     kw = dict(seed=0xFACE + n, faulty_mode=L.FAULTY_RANDOM, f=(n - 1) // 3 + 1,
               order_mode=L.ORDER_RANDOM, first_trial=64 * 9)
     od, oo, ocnt = oracle_c.run(n, m, B, **kw)
@@ -585,17 +594,34 @@ def test_levels_small_batch_fusions_vs_oracle(monkeypatch, n, m, B):
         monkeypatch.setenv("BA_NO_INPUT_FUSION", off_in)
         monkeypatch.setenv("BA_NO_LEAF_UP", off_up)
         monkeypatch.setenv("BA_NO_TAIL", off_tail)
+        want = OL.levels_kernels(n, me, leaf, words, no_in=off_in == "1", no_up=off_up == "1",
+                                 no_tail=off_tail == "1").names
+        # the rule, spelt out for the three toggled kernels
+        assert ("k_input" in want) == (off_in == "1" or words > 2)
+        assert ("k_leaf_up" in want) == (leaf and me >= 3 and off_up == "0")
+        assert ("k_leaf" in want) == (leaf and not (me >= 3 and off_up == "0"))
+        if "k_tail" in want:
+            assert off_tail == "0" and words <= 16
         e = L.Engine(0)
         try:
+            e.profile(True)
             res = e.run(n, m, B, engine=L.ENGINE_LEVELS, **kw)
+            names = set(e.profile_read())
+            assert names == want, f"drawn, no_fusion={off}: {sorted(names)} != {sorted(want)}"
             same(res.decisions, od, f"drawn, no_fusion={off}")
             same(res.outcome, oo, f"drawn, no_fusion={off}")
             assert {k: res.counters[k] for k in ocnt} == ocnt
+            e.profile(True)
             res = e.run(n, m, B, seed=3, faulty=fm, order=oc, engine=L.ENGINE_LEVELS)
+            names = set(e.profile_read())
+            assert names == want, f"given, no_fusion={off}: {sorted(names)} != {sorted(want)}"
             same(res.decisions, gd, f"given, no_fusion={off}")
             assert {k: res.counters[k] for k in gcnt} == gcnt
         finally:
             e.close()
+        seen.add(frozenset(want & {"k_input", "k_leaf_up", "k_leaf", "k_tail"}))
+    # at least one switch bites at every listed shape: the six combinations are not one
+    assert len(seen) >= 2, seen
 
 
 def test_two_ctxs_in_flight_equal_one_stream():

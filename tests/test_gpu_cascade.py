@@ -29,11 +29,27 @@ def _check(res, n, m, B, **kw):
 @pytest.mark.parametrize("n,m", SHAPES)
 @pytest.mark.parametrize("B", [1, 70, 700])
 def test_cascade_matches_oracle(engine, n, m, B):
+    """The kernel profile says what ran: a k_cascade* launch at every shape but (16, 3).
+    There S = n - m_eff = 13 is more than the leaf kernels' 12, the dispatch requires leaf
+    fusion for the cascade, and the call takes the multi-launch pipeline with materialised
+    leaves: k_cascade<16, 3> is compiled and never launched."""
+    import om_lattice as OL
     from ba_amd import lib as L
     kw = dict(seed=0xBA5EED + B, faulty_mode=L.FAULTY_RANDOM, f=(n - 1) // 3 + 1,
               order_mode=L.ORDER_RANDOM, first_trial=64 * 3)
-    res = engine.run(n, m, B, engine=L.ENGINE_LEVELS, **kw)
+    engine.profile(True)
+    try:
+        res = engine.run(n, m, B, engine=L.ENGINE_LEVELS, **kw)
+        names = OL.normalise(engine.profile_read())
+    finally:
+        engine.profile(False)
     _check(res, n, m, B, **kw)
+    assert names == OL.expect(n, m, "LEVELS", OL.words_of(B)).names, names
+    if (n, m) == (16, 3):
+        assert not any(k.startswith("k_cascade") for k in names), names
+        assert {"k_relay_top", "k_relay_leaf", "k_majority_leaf", "k_tail"} <= names, names
+    else:
+        assert names and all(k.startswith("k_cascade") for k in names), names
 
 
 @pytest.mark.parametrize("n,m", [(16, 5), (10, 3), (9, 4)])
