@@ -323,23 +323,31 @@ class Engine:
                                                 _ptr(out), ctypes.byref(cnt)))
         return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])))
 
+    def _run_protocol(self, fn, policy, params, batch, faulty, order, want_decisions, want_outcome,
+                      extra=None):
+        """The host entry `fn` of one wave protocol over `batch` trials of `params`
+        (make_params' arguments).  policy: the argument after params, () when the entry has
+        none.  extra: (dtype, wanted) of the entry's one further per-trial output, None when
+        it has none.  Returns (decisions, outcome, counters, extra array)."""
+        faulty = None if faulty is None else np.ascontiguousarray(faulty, dtype=np.uint32)
+        order = None if order is None else np.ascontiguousarray(order, dtype=np.uint8)
+        dec = np.zeros(batch, np.uint64) if want_decisions else None
+        out = np.zeros(batch, np.uint8) if want_outcome else None
+        ext = np.zeros(batch, extra[0]) if extra and extra[1] else None
+        p = make_params(*params)
+        cnt = Counters()
+        _check(self.lib, fn(self.handle, ctypes.byref(p), *policy, batch, _ptr(faulty), _ptr(order),
+                            _ptr(dec), _ptr(out), *((_ptr(ext),) if extra else ()), ctypes.byref(cnt)))
+        return dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])), ext
+
     def run_sm(self, n, m, batch, seed=0, lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN, f=0,
                order_mode=ORDER_GIVEN, order_value=ATTACK, first_trial=0, faulty=None, order=None,
                want_decisions=True, want_outcome=True, want_vsets=False) -> RunResult:
         """Resolve `batch` SM(m) signed-messages trials (docs/SEMANTICS.md §6) through
         host buffers; the same inputs as `run` with equal keywords."""
-        faulty = None if faulty is None else np.ascontiguousarray(faulty, dtype=np.uint32)
-        order = None if order is None else np.ascontiguousarray(order, dtype=np.uint8)
-        dec = np.zeros(batch, np.uint64) if want_decisions else None
-        out = np.zeros(batch, np.uint8) if want_outcome else None
-        vs = np.zeros(batch, np.uint64) if want_vsets else None
-        p = make_params(n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, ENGINE_AUTO,
-                        first_trial)
-        cnt = Counters()
-        _check(self.lib, self.lib.ba_sm_run_trials(self.handle, ctypes.byref(p), batch, _ptr(faulty),
-                                                   _ptr(order), _ptr(dec), _ptr(out), _ptr(vs),
-                                                   ctypes.byref(cnt)))
-        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])), vs)
+        params = (n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, ENGINE_AUTO, first_trial)
+        return RunResult(*self._run_protocol(self.lib.ba_sm_run_trials, (), params, batch, faulty, order,
+                                             want_decisions, want_outcome, (np.uint64, want_vsets)))
 
     def run_sm_device(self, params: Params, batch: int, d_faulty=0, d_order=0, d_decisions=0,
                       d_outcome=0, d_vsets=0, d_counters=0, stream=0):
@@ -356,17 +364,9 @@ class Engine:
         """Resolve `batch` OM(m) trials whose traitors follow a scripted policy (ADV_SPLIT,
         ADV_FLIP, ADV_ANTI; docs/SEMANTICS.md §7) through host buffers; the same inputs as
         `run` with equal keywords."""
-        faulty = None if faulty is None else np.ascontiguousarray(faulty, dtype=np.uint32)
-        order = None if order is None else np.ascontiguousarray(order, dtype=np.uint8)
-        dec = np.zeros(batch, np.uint64) if want_decisions else None
-        out = np.zeros(batch, np.uint8) if want_outcome else None
-        p = make_params(n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, engine,
-                        first_trial)
-        cnt = Counters()
-        _check(self.lib, self.lib.ba_adv_run_trials(self.handle, ctypes.byref(p), policy, batch,
-                                                    _ptr(faulty), _ptr(order), _ptr(dec), _ptr(out),
-                                                    ctypes.byref(cnt)))
-        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])))
+        params = (n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, engine, first_trial)
+        return RunResult(*self._run_protocol(self.lib.ba_adv_run_trials, (policy,), params, batch, faulty,
+                                             order, want_decisions, want_outcome)[:3])
 
     def run_adv_device(self, params: Params, batch: int, policy: int, d_faulty=0, d_order=0,
                        d_decisions=0, d_outcome=0, d_counters=0, stream=0):
@@ -382,18 +382,11 @@ class Engine:
                  want_outcome=True, want_settled=False) -> RunResult:
         """Resolve `batch` Phase King trials (KING_COIN, KING_SPLIT; docs/SEMANTICS.md §9)
         through host buffers; the same inputs as `run` with equal keywords."""
-        faulty = None if faulty is None else np.ascontiguousarray(faulty, dtype=np.uint32)
-        order = None if order is None else np.ascontiguousarray(order, dtype=np.uint8)
-        dec = np.zeros(batch, np.uint64) if want_decisions else None
-        out = np.zeros(batch, np.uint8) if want_outcome else None
-        stl = np.zeros(batch, np.uint8) if want_settled else None
-        p = make_params(n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, engine,
-                        first_trial)
-        cnt = Counters()
-        _check(self.lib, self.lib.ba_king_run_trials(self.handle, ctypes.byref(p), policy, batch,
-                                                     _ptr(faulty), _ptr(order), _ptr(dec), _ptr(out),
-                                                     _ptr(stl), ctypes.byref(cnt)))
-        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])), settled=stl)
+        params = (n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, engine, first_trial)
+        dec, out, cnt, stl = self._run_protocol(self.lib.ba_king_run_trials, (policy,), params, batch, faulty,
+                                                order, want_decisions, want_outcome,
+                                                (np.uint8, want_settled))
+        return RunResult(dec, out, cnt, settled=stl)
 
     def run_king_device(self, params: Params, batch: int, policy: int, d_faulty=0, d_order=0,
                         d_decisions=0, d_outcome=0, d_settled=0, d_counters=0, stream=0):
@@ -411,18 +404,11 @@ class Engine:
         """Resolve `batch` trials of the three-round King algorithm (KING_COIN, KING_SPLIT;
         docs/SEMANTICS.md §10; m <= 10) through host buffers; the same inputs as `run`
         and `run_king` with equal keywords."""
-        faulty = None if faulty is None else np.ascontiguousarray(faulty, dtype=np.uint32)
-        order = None if order is None else np.ascontiguousarray(order, dtype=np.uint8)
-        dec = np.zeros(batch, np.uint64) if want_decisions else None
-        out = np.zeros(batch, np.uint8) if want_outcome else None
-        stl = np.zeros(batch, np.uint8) if want_settled else None
-        p = make_params(n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, engine,
-                        first_trial)
-        cnt = Counters()
-        _check(self.lib, self.lib.ba_king3_run_trials(self.handle, ctypes.byref(p), policy, batch,
-                                                      _ptr(faulty), _ptr(order), _ptr(dec), _ptr(out),
-                                                      _ptr(stl), ctypes.byref(cnt)))
-        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])), settled=stl)
+        params = (n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, engine, first_trial)
+        dec, out, cnt, stl = self._run_protocol(self.lib.ba_king3_run_trials, (policy,), params, batch, faulty,
+                                                order, want_decisions, want_outcome,
+                                                (np.uint8, want_settled))
+        return RunResult(dec, out, cnt, settled=stl)
 
     def run_king3_device(self, params: Params, batch: int, policy: int, d_faulty=0, d_order=0,
                          d_decisions=0, d_outcome=0, d_settled=0, d_counters=0, stream=0):

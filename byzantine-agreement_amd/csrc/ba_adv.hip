@@ -28,7 +28,7 @@
 // ballot) -> walk (lane = item) -> epilogue (lane = trial: decision planes
 // picked out of LDS, trial_result, counters).  HBM traffic is the 5 B in and
 // 9 B out per trial.
-#include "ba_engine.hpp"
+#include "ba_wave_proto.hpp"
 
 namespace ba {
 
@@ -156,35 +156,6 @@ __device__ __forceinline__ uint64_t adv_resolve(const AdvPair* __restrict__ tab0
     }
 }
 
-// Wave totals of one word's run counters added into `mine` (lane c holds counter
-// c): flags by ballot + popcount, the small integers bit-sliced (faulty_total up
-// to 32 per trial: six planes).
-__device__ __forceinline__ void adv_counts_add(bool live, const TrialResult& r, uint32_t lane,
-                                               uint64_t& mine) {
-    const uint32_t o = r.out, q = o & 3;
-    const bool agree = (o >> 2) & 1, appl = (o >> 3) & 1, valid = (o >> 4) & 1, inb = (o >> 5) & 1;
-    uint32_t c[C_NUM];
-    c[C_TRIALS] = __popcll(__ballot(live));
-    c[C_AGREE] = __popcll(__ballot(live && agree));
-    c[C_VAPPL] = __popcll(__ballot(live && appl));
-    c[C_VALID] = __popcll(__ballot(live && valid));
-    c[C_QR] = __popcll(__ballot(live && q == 0));
-    c[C_QA] = __popcll(__ballot(live && q == 1));
-    c[C_QU] = __popcll(__ballot(live && q == 2));
-    c[C_INB] = __popcll(__ballot(live && inb));
-    c[C_VIOL] = __popcll(__ballot(live && inb && (!agree || (appl && !valid))));
-    c[C_UNDEF] = c[C_FTOT] = c[C_ATT] = 0;
-#pragma unroll
-    for (int b = 0; b < 6; ++b) {
-        c[C_UNDEF] += (uint32_t)__popcll(__ballot(live && ((r.nU >> b) & 1u))) << b;
-        c[C_FTOT] += (uint32_t)__popcll(__ballot(live && ((r.nf >> b) & 1u))) << b;
-        c[C_ATT] += (uint32_t)__popcll(__ballot(live && ((r.nA >> b) & 1u))) << b;
-    }
-#pragma unroll
-    for (int i = 0; i < C_NUM; ++i)
-        if (lane == (uint32_t)i) mine += c[i];
-}
-
 template <int ME, bool FLIP>
 __global__ __launch_bounds__(kAdvThreads) void k_adv(uint32_t n, uint32_t anti, uint32_t wpb,
                                                      uint64_t seed, GenSpec gen,
@@ -203,7 +174,7 @@ __global__ __launch_bounds__(kAdvThreads) void k_adv(uint32_t n, uint32_t anti, 
     uint32_t* const fms = reinterpret_cast<uint32_t*>(hdr + wpb);  // [wpb][64]
     uint8_t* const ocs = reinterpret_cast<uint8_t*>(fms + wpb * 64u);  // [wpb][64]
     const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
+    const uint32_t all = general_mask(n);
     const uint64_t words = (batch + 63) / 64, nblk = (words + wpb - 1) / wpb;
     const uint32_t nwaves = gridDim.x * (kAdvThreads / 64), gwave = blockIdx.x * (kAdvThreads / 64) + wv;
     // this thread's item: receiver r of the block's word lw
@@ -216,17 +187,12 @@ __global__ __launch_bounds__(kAdvThreads) void k_adv(uint32_t n, uint32_t anti, 
         for (uint32_t q = wv; q < wpb; q += kAdvThreads / 64) {
             const uint64_t i = (w0 + q) * 64 + lane;
             const bool live = w0 + q < words && i < batch;
-            uint32_t fm = 0, oc = 0;
-            if (live) {
-                if (gen.faulty_mode == 0) fm = faulty[i];
-                if (gen.order_mode == 0) oc = order[i];
-                gen_trial(n, seed, gen, first_trial + i, fm, oc);
-            }
-            fm &= all;
+            uint32_t fm, oc;
+            trial_inputs<true>(live, n, all, seed, gen, first_trial, i, faulty, order, fm, oc);
             const uint64_t F0 = __ballot((fm & 1u) != 0), OB = __ballot(oc == 1);
             uint64_t myF = 0;
             for (uint32_t g = 1; g < n; ++g) {
-                const uint64_t pl = __ballot(((fm >> g) & 1u) != 0);
+                const uint64_t pl = faulty_plane(fm, g);
                 if (lane == g - 1) myF = pl;
             }
             if (lane < L) {
@@ -246,7 +212,7 @@ __global__ __launch_bounds__(kAdvThreads) void k_adv(uint32_t n, uint32_t anti, 
             const AdvPair* const t0 = tab0 + lw * L;
             const AdvPair* const t1 = tab1 + lw * L;
             const uint64_t g0r = FLIP ? 0ull : t0[r].b, g1r = FLIP ? 0ull : t1[r].b;
-            const uint32_t lts = L >= 32 ? 0xFFFFFFFFu : ((1u << L) - 1u);
+            const uint32_t lts = general_mask(L);
             uint64_t tie = 0;
             const uint64_t A = adv_resolve<0, ME, FLIP>(t0, t1, h.b, h.a, g0r, g1r,
                                                         lts & ~(1u << r), L, tie);
@@ -272,7 +238,7 @@ __global__ __launch_bounds__(kAdvThreads) void k_adv(uint32_t n, uint32_t anti, 
                 if (decisions) decisions[i] = res.dec;
                 if (outcome) outcome[i] = (uint8_t)res.out;
             }
-            adv_counts_add(live, res, lane, mine);
+            lane_counts_add<true>(live, res, lane, mine);
         }
         __syncthreads();  // the next pass restages the tables
     }

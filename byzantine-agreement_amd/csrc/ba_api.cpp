@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -18,6 +19,8 @@
 
 #include "../../include/ba.h"
 #include "ba_engine.hpp"
+#include "ba_host_plan.hpp"
+#include "ba_wave_proto.hpp"
 
 using namespace ba;
 
@@ -1036,17 +1039,133 @@ extern "C" int ba_run_trials_device(ba_ctx* ctx, const ba_params* p, uint64_t ba
 }
 
 // ---------------------------------------------------------------------------
+// The wave protocols beside OM(m): SM, ADV, KING, KING3, ENUM.  A protocol is its
+// validation tail (validate_protocol plus what only it checks), a device entry
+// (protocol_device_entry with its launch) and a host entry (host_run with a
+// HostRun that says what it stages and how a chunk is queued).
+// ---------------------------------------------------------------------------
+// The checks every protocol shares, in the order that decides which error wins;
+// `what` names the protocol in the two messages of its own.
+static int validate_protocol(const ba_params* p, uint64_t batch, bool has_faulty, bool has_order,
+                             const char* what, uint32_t max_m = BA_MAX_DEPTH) {
+    if (!p) return fail(BA_EINVAL, "params is NULL");
+    if (p->lie_mode == BA_LIE_TABLE)
+        return fail(BA_ENOTSUP, "%s takes no coin table: its coins, if any, are Philox's (no table mode)",
+                    what);
+    int rc = validate(p, batch, has_faulty, has_order, false, max_m);
+    if (rc != BA_OK) return rc;
+    if (p->engine != BA_ENGINE_AUTO)
+        return fail(BA_EINVAL, "engine=%u: %s has one engine (BA_ENGINE_AUTO)", p->engine, what);
+    return BA_OK;
+}
+
+// The body of a protocol's device entry: ordered on the ctx, check() first, then
+// one launch(args) over the whole batch.
+template <typename Check, typename Launch>
+static int protocol_device_entry(ba_ctx* ctx, const ba_params* p, uint64_t batch,
+                                 const uint32_t* d_faulty, const uint8_t* d_order,
+                                 uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_counters,
+                                 void* stream, Check&& check, Launch&& launch) {
+    return ordered(ctx, stream, [&] {
+        int rc = check();
+        if (rc != BA_OK) return rc;
+        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
+        if (batch == 0) return BA_OK;
+        // make_args sizes nothing by m: a.me = min(m, n - 2) is a number only OM(m)'s kernels read
+        const RunArgs a = make_args(ctx, p, batch, d_faulty, d_order, nullptr, nullptr, d_decisions,
+                                    d_outcome, d_counters, stream);
+        HIP_TRY(launch(a));
+        return BA_OK;
+    });
+}
+
+// A protocol's host entry: copy in, run, copy out, in chunks of at most
+// kHostChunk trials so the ctx's staging buffers stay bounded whatever the batch
+// (the kernels take any batch in one launch; counters are zeroed once and
+// accumulate across the chunks on the device, trials keyed by their global index).
+constexpr uint64_t kHostChunk = 1ull << 24;
+
+// One chunk queued on the ctx stream: the params with the chunk's first_trial, its
+// trials, the staged inputs and outputs (NULL where not given / not asked for), the
+// extra plane, the counters with the tail words after them.
+using HostQueue = std::function<int(const ba_params&, uint64_t, const uint32_t*, const uint8_t*,
+                                    uint64_t*, uint8_t*, void*, uint64_t*, hipStream_t)>;
+
+struct HostRun {
+    const uint32_t* faulty = nullptr;  // host inputs, copied in where the mode is GIVEN
+    const uint8_t* order = nullptr;
+    uint64_t* decisions = nullptr;  // host outputs, each optional
+    uint8_t* outcome = nullptr;
+    ba_counters* counters = nullptr;
+    // at most one more per-trial output (SM's V sets, King's settled phase):
+    // extra_elem bytes per trial, staged behind the decisions in io_dec or behind
+    // the outcome in io_out (ba_host_plan.hpp)
+    void* extra = nullptr;
+    size_t extra_elem = 0;
+    bool extra_behind_dec = false;
+    const char* chunk_env = nullptr;   // tests: chunk a small batch (a multiple of 64)
+    uint64_t chunk = kHostChunk;       // without the override
+    uint64_t* tail = nullptr;          // enum: the word after the counters, preset to all-ones
+    std::function<int(hipStream_t)> before;  // enum: once, ahead of the first chunk
+    HostQueue queue;
+};
+
+// Called after validation, with batch > 0.
+static int host_run(ba_ctx* ctx, const ba_params* p, uint64_t batch, const HostRun& r) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx_order(ctx, st));  // the io buffers follow the ctx's last call
+    const bool need_f = r.faulty && p->faulty_mode == BA_FAULTY_GIVEN;
+    const bool need_o = r.order && p->order_mode == BA_ORDER_GIVEN;
+    const HostPlan h = host_plan(batch, r.chunk, getenv(r.chunk_env), r.decisions != nullptr,
+                                 r.outcome != nullptr, r.extra != nullptr, r.extra_elem,
+                                 r.extra_behind_dec);
+    const size_t cnt_bytes = (BA_NCOUNTERS + (r.tail ? 1 : 0)) * 8;
+    int rc;
+    if (need_f && (rc = ctx->io_faulty.grow(h.chunk * 4)) != BA_OK) return rc;
+    if (need_o && (rc = ctx->io_order.grow(h.chunk)) != BA_OK) return rc;
+    if (h.dec_bytes && (rc = ctx->io_dec.grow(h.dec_bytes)) != BA_OK) return rc;
+    if (h.out_bytes && (rc = ctx->io_out.grow(h.out_bytes)) != BA_OK) return rc;
+    if ((rc = ctx->io_cnt.grow(cnt_bytes)) != BA_OK) return rc;
+    uint64_t* const d_dec = (uint64_t*)ctx->io_dec.p;
+    uint8_t* const d_out = (uint8_t*)ctx->io_out.p;
+    uint64_t* const d_cnt = (uint64_t*)ctx->io_cnt.p;
+    char* const extra_base = (char*)(r.extra_behind_dec ? ctx->io_dec.p : ctx->io_out.p);
+    void* const d_extra = r.extra ? extra_base + h.extra_off : nullptr;
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, BA_NCOUNTERS * 8, st));
+    if (r.tail) HIP_TRY(hipMemsetAsync(d_cnt + BA_NCOUNTERS, 0xFF, 8, st));
+    if (r.before && (rc = r.before(st)) != BA_OK) return rc;
+    ba_params q = *p;
+    for (uint64_t t0 = 0; t0 < batch; t0 += h.chunk) {
+        const uint64_t nt = chunk_trials(batch, t0, h.chunk);
+        q.first_trial = p->first_trial + t0;
+        if (need_f)
+            HIP_TRY(hipMemcpyAsync(ctx->io_faulty.p, r.faulty + t0, nt * 4, hipMemcpyHostToDevice, st));
+        if (need_o) HIP_TRY(hipMemcpyAsync(ctx->io_order.p, r.order + t0, nt, hipMemcpyHostToDevice, st));
+        rc = r.queue(q, nt, need_f ? (const uint32_t*)ctx->io_faulty.p : nullptr,
+                     need_o ? (const uint8_t*)ctx->io_order.p : nullptr, r.decisions ? d_dec : nullptr,
+                     r.outcome ? d_out : nullptr, d_extra, d_cnt, st);
+        if (rc != BA_OK) return rc;
+        if (r.decisions)
+            HIP_TRY(hipMemcpyAsync(r.decisions + t0, d_dec, nt * 8, hipMemcpyDeviceToHost, st));
+        if (r.outcome) HIP_TRY(hipMemcpyAsync(r.outcome + t0, d_out, nt, hipMemcpyDeviceToHost, st));
+        if (r.extra)
+            HIP_TRY(hipMemcpyAsync((char*)r.extra + t0 * r.extra_elem, d_extra, nt * r.extra_elem,
+                                   hipMemcpyDeviceToHost, st));
+    }
+    uint64_t h_cnt[BA_NCOUNTERS + 1];
+    HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (r.counters) memcpy(r.counters->v, h_cnt, BA_NCOUNTERS * 8);
+    if (r.tail) *r.tail = h_cnt[BA_NCOUNTERS];
+    return BA_OK;
+}
+
+// ---------------------------------------------------------------------------
 // SM(m), signed messages (docs/SEMANTICS.md §6; ba_sm.hip)
 // ---------------------------------------------------------------------------
 static int validate_sm(const ba_params* p, uint64_t batch, bool has_faulty, bool has_order) {
-    if (!p) return fail(BA_EINVAL, "params is NULL");
-    if (p->lie_mode == BA_LIE_TABLE)
-        return fail(BA_ENOTSUP, "SM(m) draws its coins from Philox only (no table mode)");
-    int rc = validate(p, batch, has_faulty, has_order, false);
-    if (rc != BA_OK) return rc;
-    if (p->engine != BA_ENGINE_AUTO)
-        return fail(BA_EINVAL, "engine=%u: SM(m) has one engine (BA_ENGINE_AUTO)", p->engine);
-    return BA_OK;
+    return validate_protocol(p, batch, has_faulty, has_order, "SM(m)");
 }
 
 extern "C" uint64_t ba_sm_coin_calls(uint32_t n, uint32_t m) {
@@ -1059,24 +1178,13 @@ extern "C" int ba_sm_run_trials_device(ba_ctx* ctx, const ba_params* p, uint64_t
                                        const uint32_t* d_faulty, const uint8_t* d_order,
                                        uint64_t* d_decisions, uint8_t* d_outcome,
                                        uint64_t* d_vsets, uint64_t* d_counters, void* stream) {
-    return ordered(ctx, stream, [&] {
-        int rc = validate_sm(p, batch, d_faulty != nullptr, d_order != nullptr);
-        if (rc != BA_OK) return rc;
-        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
-        if (batch == 0) return BA_OK;
-        const RunArgs a = make_args(ctx, p, batch, d_faulty, d_order, nullptr, nullptr, d_decisions,
-                                    d_outcome, d_counters, stream);
-        HIP_TRY(launch_sm(a, d_vsets));
-        return BA_OK;
-    });
+    return protocol_device_entry(
+        ctx, p, batch, d_faulty, d_order, d_decisions, d_outcome, d_counters, stream,
+        [&] { return validate_sm(p, batch, d_faulty != nullptr, d_order != nullptr); },
+        [&](const RunArgs& a) { return launch_sm(a, d_vsets); });
 }
 
-// Host entry: copy in, run, copy out, in chunks of at most kSmHostChunk trials
-// so the ctx's staging buffers stay bounded whatever the batch (the kernel
-// itself takes any batch in one launch; counters accumulate across the chunks
-// on the device, trials keyed by their global index).
-constexpr uint64_t kSmHostChunk = 1ull << 24;
-
+// decisions and V sets share io_dec: [chunk] decisions, then [chunk] vsets
 extern "C" int ba_sm_run_trials(ba_ctx* ctx, const ba_params* p, uint64_t batch,
                                 const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
                                 uint8_t* outcome, uint64_t* vsets, ba_counters* counters) {
@@ -1085,47 +1193,15 @@ extern "C" int ba_sm_run_trials(ba_ctx* ctx, const ba_params* p, uint64_t batch,
     if (rc != BA_OK) return rc;
     if (counters) memset(counters, 0, sizeof *counters);
     if (batch == 0) return BA_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx_order(ctx, st));  // the io buffers follow the ctx's last call
-    const bool need_f = p->faulty_mode == BA_FAULTY_GIVEN, need_o = p->order_mode == BA_ORDER_GIVEN;
-    uint64_t chunk = kSmHostChunk;
-    if (const char* e = getenv("BA_SM_HOST_CHUNK")) {  // tests: chunk a small batch (multiple of 64)
-        const uint64_t c = strtoull(e, nullptr, 0) & ~63ull;
-        if (c) chunk = c;
-    }
-    if (chunk > batch) chunk = batch;
-    if (need_f && (rc = ctx->io_faulty.grow(chunk * 4)) != BA_OK) return rc;
-    if (need_o && (rc = ctx->io_order.grow(chunk)) != BA_OK) return rc;
-    // decisions and V sets share io_dec: [chunk] decisions, then [chunk] vsets
-    if ((decisions || vsets) && (rc = ctx->io_dec.grow(chunk * 16)) != BA_OK) return rc;
-    if (outcome && (rc = ctx->io_out.grow(chunk)) != BA_OK) return rc;
-    if ((rc = ctx->io_cnt.grow(BA_NCOUNTERS * 8)) != BA_OK) return rc;
-    uint64_t* d_dec = (uint64_t*)ctx->io_dec.p;
-    uint64_t* d_vs = d_dec ? d_dec + chunk : nullptr;
-    HIP_TRY(hipMemsetAsync(ctx->io_cnt.p, 0, BA_NCOUNTERS * 8, st));
-    ba_params q = *p;
-    for (uint64_t t0 = 0; t0 < batch; t0 += chunk) {
-        const uint64_t nt = batch - t0 < chunk ? batch - t0 : chunk;
-        q.first_trial = p->first_trial + t0;
-        if (need_f)
-            HIP_TRY(hipMemcpyAsync(ctx->io_faulty.p, faulty + t0, nt * 4, hipMemcpyHostToDevice, st));
-        if (need_o) HIP_TRY(hipMemcpyAsync(ctx->io_order.p, order + t0, nt, hipMemcpyHostToDevice, st));
-        rc = ba_sm_run_trials_device(ctx, &q, nt, need_f ? (const uint32_t*)ctx->io_faulty.p : nullptr,
-                                     need_o ? (const uint8_t*)ctx->io_order.p : nullptr,
-                                     decisions ? d_dec : nullptr,
-                                     outcome ? (uint8_t*)ctx->io_out.p : nullptr,
-                                     vsets ? d_vs : nullptr, (uint64_t*)ctx->io_cnt.p, st);
-        if (rc != BA_OK) return rc;
-        if (decisions) HIP_TRY(hipMemcpyAsync(decisions + t0, d_dec, nt * 8, hipMemcpyDeviceToHost, st));
-        if (vsets) HIP_TRY(hipMemcpyAsync(vsets + t0, d_vs, nt * 8, hipMemcpyDeviceToHost, st));
-        if (outcome) HIP_TRY(hipMemcpyAsync(outcome + t0, ctx->io_out.p, nt, hipMemcpyDeviceToHost, st));
-    }
-    uint64_t h_cnt[BA_NCOUNTERS];
-    HIP_TRY(hipMemcpyAsync(h_cnt, ctx->io_cnt.p, BA_NCOUNTERS * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (counters) memcpy(counters->v, h_cnt, sizeof h_cnt);
-    return BA_OK;
+    HostRun r;
+    r.faulty = faulty, r.order = order, r.decisions = decisions, r.outcome = outcome, r.counters = counters;
+    r.extra = vsets, r.extra_elem = 8, r.extra_behind_dec = true;
+    r.chunk_env = "BA_SM_HOST_CHUNK";
+    r.queue = [ctx](const ba_params& q, uint64_t nt, const uint32_t* d_f, const uint8_t* d_o,
+                    uint64_t* d_dec, uint8_t* d_out, void* d_extra, uint64_t* d_cnt, hipStream_t st) {
+        return ba_sm_run_trials_device(ctx, &q, nt, d_f, d_o, d_dec, d_out, (uint64_t*)d_extra, d_cnt, st);
+    };
+    return host_run(ctx, p, batch, r);
 }
 
 // ---------------------------------------------------------------------------
@@ -1143,13 +1219,8 @@ extern "C" uint64_t ba_adv_paths(uint32_t n, uint32_t m) {
 
 static int validate_adv(const ba_params* p, uint32_t policy, uint64_t batch, bool has_faulty,
                         bool has_order) {
-    if (!p) return fail(BA_EINVAL, "params is NULL");
-    if (p->lie_mode == BA_LIE_TABLE)
-        return fail(BA_ENOTSUP, "a scripted policy draws no coins (no table mode)");
-    int rc = validate(p, batch, has_faulty, has_order, false);
+    int rc = validate_protocol(p, batch, has_faulty, has_order, "a scripted policy");
     if (rc != BA_OK) return rc;
-    if (p->engine != BA_ENGINE_AUTO)
-        return fail(BA_EINVAL, "engine=%u: the policies have one engine (BA_ENGINE_AUTO)", p->engine);
     if (policy > BA_ADV_ANTI) return fail(BA_EINVAL, "policy=%u", policy);
     const uint64_t paths = ba_adv_paths(p->n, p->m);
     if (paths > kAdvMaxPaths)
@@ -1162,22 +1233,11 @@ extern "C" int ba_adv_run_trials_device(ba_ctx* ctx, const ba_params* p, uint32_
                                         uint64_t batch, const uint32_t* d_faulty,
                                         const uint8_t* d_order, uint64_t* d_decisions,
                                         uint8_t* d_outcome, uint64_t* d_counters, void* stream) {
-    return ordered(ctx, stream, [&] {
-        int rc = validate_adv(p, policy, batch, d_faulty != nullptr, d_order != nullptr);
-        if (rc != BA_OK) return rc;
-        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
-        if (batch == 0) return BA_OK;
-        const RunArgs a = make_args(ctx, p, batch, d_faulty, d_order, nullptr, nullptr, d_decisions,
-                                    d_outcome, d_counters, stream);
-        HIP_TRY(launch_adv(a, policy));
-        return BA_OK;
-    });
+    return protocol_device_entry(
+        ctx, p, batch, d_faulty, d_order, d_decisions, d_outcome, d_counters, stream,
+        [&] { return validate_adv(p, policy, batch, d_faulty != nullptr, d_order != nullptr); },
+        [&](const RunArgs& a) { return launch_adv(a, policy); });
 }
-
-// Host entry: copy in, run, copy out, in chunks of at most kAdvHostChunk trials so
-// the ctx's staging buffers stay bounded whatever the batch (counters accumulate
-// across the chunks on the device).
-constexpr uint64_t kAdvHostChunk = 1ull << 24;
 
 extern "C" int ba_adv_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
                                  const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
@@ -1187,45 +1247,14 @@ extern "C" int ba_adv_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t polic
     if (rc != BA_OK) return rc;
     if (counters) memset(counters, 0, sizeof *counters);
     if (batch == 0) return BA_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx_order(ctx, st));  // the io buffers follow the ctx's last call
-    const bool need_f = p->faulty_mode == BA_FAULTY_GIVEN, need_o = p->order_mode == BA_ORDER_GIVEN;
-    uint64_t chunk = kAdvHostChunk;
-    if (const char* e = getenv("BA_ADV_HOST_CHUNK")) {  // tests: chunk a small batch (multiple of 64)
-        const uint64_t c = strtoull(e, nullptr, 0) & ~63ull;
-        if (c) chunk = c;
-    }
-    if (chunk > batch) chunk = batch;
-    if (need_f && (rc = ctx->io_faulty.grow(chunk * 4)) != BA_OK) return rc;
-    if (need_o && (rc = ctx->io_order.grow(chunk)) != BA_OK) return rc;
-    if (decisions && (rc = ctx->io_dec.grow(chunk * 8)) != BA_OK) return rc;
-    if (outcome && (rc = ctx->io_out.grow(chunk)) != BA_OK) return rc;
-    if ((rc = ctx->io_cnt.grow(BA_NCOUNTERS * 8)) != BA_OK) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->io_cnt.p, 0, BA_NCOUNTERS * 8, st));
-    ba_params q = *p;
-    for (uint64_t t0 = 0; t0 < batch; t0 += chunk) {
-        const uint64_t nt = batch - t0 < chunk ? batch - t0 : chunk;
-        q.first_trial = p->first_trial + t0;
-        if (need_f)
-            HIP_TRY(hipMemcpyAsync(ctx->io_faulty.p, faulty + t0, nt * 4, hipMemcpyHostToDevice, st));
-        if (need_o) HIP_TRY(hipMemcpyAsync(ctx->io_order.p, order + t0, nt, hipMemcpyHostToDevice, st));
-        rc = ba_adv_run_trials_device(ctx, &q, policy, nt,
-                                      need_f ? (const uint32_t*)ctx->io_faulty.p : nullptr,
-                                      need_o ? (const uint8_t*)ctx->io_order.p : nullptr,
-                                      decisions ? (uint64_t*)ctx->io_dec.p : nullptr,
-                                      outcome ? (uint8_t*)ctx->io_out.p : nullptr,
-                                      (uint64_t*)ctx->io_cnt.p, st);
-        if (rc != BA_OK) return rc;
-        if (decisions)
-            HIP_TRY(hipMemcpyAsync(decisions + t0, ctx->io_dec.p, nt * 8, hipMemcpyDeviceToHost, st));
-        if (outcome) HIP_TRY(hipMemcpyAsync(outcome + t0, ctx->io_out.p, nt, hipMemcpyDeviceToHost, st));
-    }
-    uint64_t h_cnt[BA_NCOUNTERS];
-    HIP_TRY(hipMemcpyAsync(h_cnt, ctx->io_cnt.p, BA_NCOUNTERS * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (counters) memcpy(counters->v, h_cnt, sizeof h_cnt);
-    return BA_OK;
+    HostRun r;
+    r.faulty = faulty, r.order = order, r.decisions = decisions, r.outcome = outcome, r.counters = counters;
+    r.chunk_env = "BA_ADV_HOST_CHUNK";
+    r.queue = [ctx, policy](const ba_params& q, uint64_t nt, const uint32_t* d_f, const uint8_t* d_o,
+                            uint64_t* d_dec, uint8_t* d_out, void*, uint64_t* d_cnt, hipStream_t st) {
+        return ba_adv_run_trials_device(ctx, &q, policy, nt, d_f, d_o, d_dec, d_out, d_cnt, st);
+    };
+    return host_run(ctx, p, batch, r);
 }
 
 // ---------------------------------------------------------------------------
@@ -1247,13 +1276,8 @@ extern "C" uint64_t ba_king_coin_calls(uint32_t n, uint32_t m) {
 
 static int validate_king(const ba_params* p, uint32_t policy, uint64_t batch, bool has_faulty,
                          bool has_order) {
-    if (!p) return fail(BA_EINVAL, "params is NULL");
-    if (p->lie_mode == BA_LIE_TABLE)
-        return fail(BA_ENOTSUP, "Phase King draws its coins from Philox only (no table mode)");
-    int rc = validate(p, batch, has_faulty, has_order, false);
+    int rc = validate_protocol(p, batch, has_faulty, has_order, "Phase King");
     if (rc != BA_OK) return rc;
-    if (p->engine != BA_ENGINE_AUTO)
-        return fail(BA_EINVAL, "engine=%u: Phase King has one engine (BA_ENGINE_AUTO)", p->engine);
     if (policy > BA_KING_SPLIT) return fail(BA_EINVAL, "policy=%u", policy);
     return BA_OK;
 }
@@ -1263,85 +1287,44 @@ extern "C" int ba_king_run_trials_device(ba_ctx* ctx, const ba_params* p, uint32
                                          const uint8_t* d_order, uint64_t* d_decisions,
                                          uint8_t* d_outcome, uint8_t* d_settled,
                                          uint64_t* d_counters, void* stream) {
-    return ordered(ctx, stream, [&] {
-        int rc = validate_king(p, policy, batch, d_faulty != nullptr, d_order != nullptr);
-        if (rc != BA_OK) return rc;
-        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
-        if (batch == 0) return BA_OK;
-        const RunArgs a = make_args(ctx, p, batch, d_faulty, d_order, nullptr, nullptr, d_decisions,
-                                    d_outcome, d_counters, stream);
-        HIP_TRY(launch_king(a, policy, ba_king_phases(p->n, p->m), d_settled));
-        return BA_OK;
-    });
+    return protocol_device_entry(
+        ctx, p, batch, d_faulty, d_order, d_decisions, d_outcome, d_counters, stream,
+        [&] { return validate_king(p, policy, batch, d_faulty != nullptr, d_order != nullptr); },
+        [&](const RunArgs& a) { return launch_king(a, policy, ba_king_phases(p->n, p->m), d_settled); });
 }
 
-// Host entry of Phase King and KING3: copy in, run, copy out, in chunks of at most
-// kKingHostChunk trials so the ctx's staging buffers stay bounded whatever the batch
-// (counters accumulate across the chunks on the device).  `check` is the protocol's
-// validation, `device_entry` its device entry, `chunk_env` the tests' chunk override.
-constexpr uint64_t kKingHostChunk = 1ull << 24;
-
+// Host entry of Phase King and KING3 (`check` is the protocol's validation,
+// `device_entry` its device entry): outcome and settled bytes share io_out,
+// [chunk] outcome, then [chunk] settled.
 using KingValidate = int (*)(const ba_params*, uint32_t, uint64_t, bool, bool);
 using KingDeviceEntry = int (*)(ba_ctx*, const ba_params*, uint32_t, uint64_t, const uint32_t*,
                                 const uint8_t*, uint64_t*, uint8_t*, uint8_t*, uint64_t*, void*);
 
-static int king_host_run(KingValidate check, KingDeviceEntry device_entry, const char* chunk_env,
-                         ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
-                         const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
-                         uint8_t* outcome, uint8_t* settled, ba_counters* counters) {
+static int king_host_entry(KingValidate check, KingDeviceEntry device_entry, const char* chunk_env,
+                           ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
+                           const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
+                           uint8_t* outcome, uint8_t* settled, ba_counters* counters) {
     if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
     int rc = check(p, policy, batch, faulty != nullptr, order != nullptr);
     if (rc != BA_OK) return rc;
     if (counters) memset(counters, 0, sizeof *counters);
     if (batch == 0) return BA_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx_order(ctx, st));  // the io buffers follow the ctx's last call
-    const bool need_f = p->faulty_mode == BA_FAULTY_GIVEN, need_o = p->order_mode == BA_ORDER_GIVEN;
-    uint64_t chunk = kKingHostChunk;
-    if (const char* e = getenv(chunk_env)) {  // tests: chunk a small batch (multiple of 64)
-        const uint64_t c = strtoull(e, nullptr, 0) & ~63ull;
-        if (c) chunk = c;
-    }
-    if (chunk > batch) chunk = batch;
-    if (need_f && (rc = ctx->io_faulty.grow(chunk * 4)) != BA_OK) return rc;
-    if (need_o && (rc = ctx->io_order.grow(chunk)) != BA_OK) return rc;
-    if (decisions && (rc = ctx->io_dec.grow(chunk * 8)) != BA_OK) return rc;
-    // outcome and settled bytes share io_out: [chunk] outcome, then [chunk] settled
-    if ((outcome || settled) && (rc = ctx->io_out.grow(chunk * 2)) != BA_OK) return rc;
-    if ((rc = ctx->io_cnt.grow(BA_NCOUNTERS * 8)) != BA_OK) return rc;
-    uint8_t* d_out = (uint8_t*)ctx->io_out.p;
-    uint8_t* d_set = d_out ? d_out + chunk : nullptr;
-    HIP_TRY(hipMemsetAsync(ctx->io_cnt.p, 0, BA_NCOUNTERS * 8, st));
-    ba_params q = *p;
-    for (uint64_t t0 = 0; t0 < batch; t0 += chunk) {
-        const uint64_t nt = batch - t0 < chunk ? batch - t0 : chunk;
-        q.first_trial = p->first_trial + t0;
-        if (need_f)
-            HIP_TRY(hipMemcpyAsync(ctx->io_faulty.p, faulty + t0, nt * 4, hipMemcpyHostToDevice, st));
-        if (need_o) HIP_TRY(hipMemcpyAsync(ctx->io_order.p, order + t0, nt, hipMemcpyHostToDevice, st));
-        rc = device_entry(ctx, &q, policy, nt, need_f ? (const uint32_t*)ctx->io_faulty.p : nullptr,
-                          need_o ? (const uint8_t*)ctx->io_order.p : nullptr,
-                          decisions ? (uint64_t*)ctx->io_dec.p : nullptr, outcome ? d_out : nullptr,
-                          settled ? d_set : nullptr, (uint64_t*)ctx->io_cnt.p, st);
-        if (rc != BA_OK) return rc;
-        if (decisions)
-            HIP_TRY(hipMemcpyAsync(decisions + t0, ctx->io_dec.p, nt * 8, hipMemcpyDeviceToHost, st));
-        if (outcome) HIP_TRY(hipMemcpyAsync(outcome + t0, d_out, nt, hipMemcpyDeviceToHost, st));
-        if (settled) HIP_TRY(hipMemcpyAsync(settled + t0, d_set, nt, hipMemcpyDeviceToHost, st));
-    }
-    uint64_t h_cnt[BA_NCOUNTERS];
-    HIP_TRY(hipMemcpyAsync(h_cnt, ctx->io_cnt.p, BA_NCOUNTERS * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (counters) memcpy(counters->v, h_cnt, sizeof h_cnt);
-    return BA_OK;
+    HostRun r;
+    r.faulty = faulty, r.order = order, r.decisions = decisions, r.outcome = outcome, r.counters = counters;
+    r.extra = settled, r.extra_elem = 1, r.extra_behind_dec = false;
+    r.chunk_env = chunk_env;
+    r.queue = [=](const ba_params& q, uint64_t nt, const uint32_t* d_f, const uint8_t* d_o,
+                  uint64_t* d_dec, uint8_t* d_out, void* d_extra, uint64_t* d_cnt, hipStream_t st) {
+        return device_entry(ctx, &q, policy, nt, d_f, d_o, d_dec, d_out, (uint8_t*)d_extra, d_cnt, st);
+    };
+    return host_run(ctx, p, batch, r);
 }
 
 extern "C" int ba_king_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
                                   const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
                                   uint8_t* outcome, uint8_t* settled, ba_counters* counters) {
-    return king_host_run(validate_king, ba_king_run_trials_device, "BA_KING_HOST_CHUNK", ctx, p, policy,
-                         batch, faulty, order, decisions, outcome, settled, counters);
+    return king_host_entry(validate_king, ba_king_run_trials_device, "BA_KING_HOST_CHUNK", ctx, p, policy,
+                           batch, faulty, order, decisions, outcome, settled, counters);
 }
 
 // ---------------------------------------------------------------------------
@@ -1363,13 +1346,8 @@ extern "C" uint64_t ba_king3_coin_calls(uint32_t n, uint32_t m) {
 
 static int validate_king3(const ba_params* p, uint32_t policy, uint64_t batch, bool has_faulty,
                           bool has_order) {
-    if (!p) return fail(BA_EINVAL, "params is NULL");
-    if (p->lie_mode == BA_LIE_TABLE)
-        return fail(BA_ENOTSUP, "KING3 draws its coins from Philox only (no table mode)");
-    int rc = validate(p, batch, has_faulty, has_order, false, kKing3MaxM);
+    int rc = validate_protocol(p, batch, has_faulty, has_order, "KING3", kKing3MaxM);
     if (rc != BA_OK) return rc;
-    if (p->engine != BA_ENGINE_AUTO)
-        return fail(BA_EINVAL, "engine=%u: KING3 has one engine (BA_ENGINE_AUTO)", p->engine);
     if (policy > BA_KING_SPLIT) return fail(BA_EINVAL, "policy=%u", policy);
     return BA_OK;
 }
@@ -1379,24 +1357,17 @@ extern "C" int ba_king3_run_trials_device(ba_ctx* ctx, const ba_params* p, uint3
                                           const uint8_t* d_order, uint64_t* d_decisions,
                                           uint8_t* d_outcome, uint8_t* d_settled,
                                           uint64_t* d_counters, void* stream) {
-    return ordered(ctx, stream, [&] {
-        int rc = validate_king3(p, policy, batch, d_faulty != nullptr, d_order != nullptr);
-        if (rc != BA_OK) return rc;
-        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
-        if (batch == 0) return BA_OK;
-        // make_args sizes nothing by m: a.me = min(m, n - 2) is a number k_king3 never reads
-        const RunArgs a = make_args(ctx, p, batch, d_faulty, d_order, nullptr, nullptr, d_decisions,
-                                    d_outcome, d_counters, stream);
-        HIP_TRY(launch_king3(a, policy, ba_king3_phases(p->n, p->m), d_settled));
-        return BA_OK;
-    });
+    return protocol_device_entry(
+        ctx, p, batch, d_faulty, d_order, d_decisions, d_outcome, d_counters, stream,
+        [&] { return validate_king3(p, policy, batch, d_faulty != nullptr, d_order != nullptr); },
+        [&](const RunArgs& a) { return launch_king3(a, policy, ba_king3_phases(p->n, p->m), d_settled); });
 }
 
 extern "C" int ba_king3_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t policy, uint64_t batch,
                                    const uint32_t* faulty, const uint8_t* order, uint64_t* decisions,
                                    uint8_t* outcome, uint8_t* settled, ba_counters* counters) {
-    return king_host_run(validate_king3, ba_king3_run_trials_device, "BA_KING3_HOST_CHUNK", ctx, p,
-                         policy, batch, faulty, order, decisions, outcome, settled, counters);
+    return king_host_entry(validate_king3, ba_king3_run_trials_device, "BA_KING3_HOST_CHUNK", ctx, p,
+                           policy, batch, faulty, order, decisions, outcome, settled, counters);
 }
 
 // ---------------------------------------------------------------------------
@@ -1407,8 +1378,7 @@ constexpr uint32_t kEnumBitsSaturated = 0xFFFFFFFEu;
 // B = [F_0](L - f_L) + f_L (L - f_L) sum_{k=1..me} P(L-2, k-1)
 extern "C" uint32_t ba_enum_bits(uint32_t n, uint32_t m, uint32_t faulty_mask) {
     if (n < 1 || n > BA_MAX_GENERALS || m > BA_MAX_DEPTH) return 0xFFFFFFFFu;
-    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
-    const uint32_t F = faulty_mask & all;
+    const uint32_t F = faulty_mask & general_mask(n);
     const uint64_t L = n - 1, me = effective_depth(n, m);
     const uint64_t fL = (uint64_t)__builtin_popcount(F >> 1), loyal = L - fL;
     uint64_t chains = 0, p = 1;  // p = P(L-2, k-1)
@@ -1439,8 +1409,7 @@ static int enum_plan(uint32_t n, uint32_t m, uint32_t faulty_mask, EnumPlan& pl)
     if (B > BA_ENUM_MAX_BITS)
         return fail(BA_ETOOBIG, "n=%u m=%u faulty_mask=0x%x: %u free bits > %d", n, m, faulty_mask, B,
                     BA_ENUM_MAX_BITS);
-    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
-    const uint32_t F = faulty_mask & all, L = n - 1, me = effective_depth(n, m);
+    const uint32_t F = faulty_mask & general_mask(n), L = n - 1, me = effective_depth(n, m);
     pl.g.n = n;
     pl.g.fmask = F;
     std::vector<std::vector<uint8_t>> cls(me + 1);  // per level, in path rank
@@ -1504,13 +1473,8 @@ constexpr uint64_t kEnumLaunchMax = 1ull << 40;
 
 static int validate_enum(const ba_params* p, uint32_t faulty_mask, uint32_t order, uint64_t batch,
                          EnumPlan& pl) {
-    if (!p) return fail(BA_EINVAL, "params is NULL");
-    if (p->lie_mode == BA_LIE_TABLE)
-        return fail(BA_ENOTSUP, "the enumeration draws no coins (no table mode)");
-    int rc = validate(p, batch, true, true, false);
+    int rc = validate_protocol(p, batch, true, true, "the enumeration");
     if (rc != BA_OK) return rc;
-    if (p->engine != BA_ENGINE_AUTO)
-        return fail(BA_EINVAL, "engine=%u: the enumeration has one engine (BA_ENGINE_AUTO)", p->engine);
     if (p->faulty_mode != BA_FAULTY_GIVEN || p->order_mode != BA_ORDER_GIVEN)
         return fail(BA_EINVAL, "faulty_mode=%u order_mode=%u: one given faulty set and order per call "
                     "(BA_FAULTY_GIVEN, BA_ORDER_GIVEN)", p->faulty_mode, p->order_mode);
@@ -1578,12 +1542,10 @@ extern "C" int ba_enum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t faul
     });
 }
 
-// Host entry: run, copy out, in chunks of at most kEnumHostChunk strategies when a
-// per-trial output is asked for, so the ctx's staging buffers stay bounded (counters
-// and the witness accumulate across the chunks on the device); counters only: one
-// chunk.  The case is planned and its slot map uploaded once for all the chunks.
-constexpr uint64_t kEnumHostChunk = 1ull << 24;
-
+// Host entry: host_run with no inputs to copy; counters only: one chunk, chunks of
+// kHostChunk strategies when a per-trial output is asked for (the witness
+// min-accumulates across them on the device, in the word after the counters).
+// The case is planned and its slot map uploaded once for all the chunks.
 extern "C" int ba_enum_run(ba_ctx* ctx, const ba_params* p, uint32_t faulty_mask, uint32_t order,
                            uint64_t batch, uint64_t* decisions, uint8_t* outcome,
                            ba_counters* counters, uint64_t* witness) {
@@ -1594,42 +1556,23 @@ extern "C" int ba_enum_run(ba_ctx* ctx, const ba_params* p, uint32_t faulty_mask
     if (counters) memset(counters, 0, sizeof *counters);
     if (witness) *witness = UINT64_MAX;
     if (batch == 0) return BA_OK;
-    HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    HIP_TRY(ctx_order(ctx, st));  // the io buffers follow the ctx's last call
-    uint64_t chunk = (decisions || outcome) ? kEnumHostChunk : batch;
-    if (const char* e = getenv("BA_ENUM_HOST_CHUNK")) {  // tests: chunk a small batch (multiple of 64)
-        const uint64_t c = strtoull(e, nullptr, 0) & ~63ull;
-        if (c) chunk = c;
-    }
-    if (chunk > batch) chunk = batch;
-    if (decisions && (rc = ctx->io_dec.grow(chunk * 8)) != BA_OK) return rc;
-    if (outcome && (rc = ctx->io_out.grow(chunk)) != BA_OK) return rc;
-    // the counters, then the witness in the word after them
-    if ((rc = ctx->io_cnt.grow((BA_NCOUNTERS + 1) * 8)) != BA_OK) return rc;
-    uint64_t* d_cnt = (uint64_t*)ctx->io_cnt.p;
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, BA_NCOUNTERS * 8, st));
-    HIP_TRY(hipMemsetAsync(d_cnt + BA_NCOUNTERS, 0xFF, 8, st));
-    rc = enum_upload(ctx, pl, st);
-    (void)ctx_mark(ctx, st);  // whatever follows: work of this ctx is queued on st
-    if (rc != BA_OK) return rc;
-    for (uint64_t t0 = 0; t0 < batch; t0 += chunk) {
-        const uint64_t nt = batch - t0 < chunk ? batch - t0 : chunk;
-        rc = enum_launch_range(ctx, p, pl, p->first_trial + t0, nt,
-                               decisions ? (uint64_t*)ctx->io_dec.p : nullptr,
-                               outcome ? (uint8_t*)ctx->io_out.p : nullptr, d_cnt,
-                               d_cnt + BA_NCOUNTERS, st);
-        if (rc != BA_OK) return rc;
-        if (decisions)
-            HIP_TRY(hipMemcpyAsync(decisions + t0, ctx->io_dec.p, nt * 8, hipMemcpyDeviceToHost, st));
-        if (outcome) HIP_TRY(hipMemcpyAsync(outcome + t0, ctx->io_out.p, nt, hipMemcpyDeviceToHost, st));
-    }
-    uint64_t h_cnt[BA_NCOUNTERS + 1];
-    HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (counters) memcpy(counters->v, h_cnt, BA_NCOUNTERS * 8);
-    if (witness) *witness = h_cnt[BA_NCOUNTERS];
-    return BA_OK;
+    uint64_t wit = UINT64_MAX;
+    HostRun r;
+    r.decisions = decisions, r.outcome = outcome, r.counters = counters, r.tail = &wit;
+    r.chunk_env = "BA_ENUM_HOST_CHUNK";
+    r.chunk = (decisions || outcome) ? kHostChunk : batch;
+    r.before = [&](hipStream_t st) {
+        const int up = enum_upload(ctx, pl, st);
+        (void)ctx_mark(ctx, st);  // whatever follows: work of this ctx is queued on st
+        return up;
+    };
+    r.queue = [&](const ba_params& q, uint64_t nt, const uint32_t*, const uint8_t*, uint64_t* d_dec,
+                  uint8_t* d_out, void*, uint64_t* d_cnt, hipStream_t st) {
+        return enum_launch_range(ctx, p, pl, q.first_trial, nt, d_dec, d_out, d_cnt, d_cnt + BA_NCOUNTERS, st);
+    };
+    rc = host_run(ctx, p, batch, r);
+    if (rc == BA_OK && witness) *witness = wit;
+    return rc;
 }
 
 extern "C" int ba_split_votes_device(ba_ctx* ctx, const ba_params* p, uint64_t batch,

@@ -33,7 +33,7 @@
 // wave's lowest violating S, one 64-bit atomic min per wave that found one.  The
 // lane = trial pick-out of decisions / outcome bytes runs only when asked for, on
 // one-wave blocks that keep the tile's decision planes in LDS.
-#include "ba_engine.hpp"
+#include "ba_wave_proto.hpp"
 
 namespace ba {
 
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kEnumThreads) void k_enum(EnumCase g, uint64_t firs
     const bool F0 = (g.fmask & 1u) != 0;
     const uint32_t oc = g.order;
     const uint64_t ob = oc == 1u ? ~0ull : 0ull;
-    const uint32_t lts = L >= 32u ? 0xFFFFFFFFu : ((1u << L) - 1u);
+    const uint32_t lts = general_mask(L);
     // quorum thresholds (§2.4): every general answers, total = n
     uint32_t needed = 2u * ((n - 1u) / 3u) + 1u;
     if (n <= 3u) needed = n - 1u;

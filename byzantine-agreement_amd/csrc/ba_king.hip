@@ -23,8 +23,8 @@
 //               consecutive: no bank conflict), read back by lane l ^ 32
 //   kmaj, agr   the king's majority plane; the loyal attack / retreat holders of `settled`
 // The DS instructions of one wave execute in issue order, so between the steps
-// only the compiler has to be held (king_wave_sync; the wave helpers are
-// ba_king_common.hpp's, shared with k_king3).
+// only the compiler has to be held (wave_sync, ba_wave_proto.hpp; the King
+// helpers are ba_king_common.hpp's, shared with k_king3).
 //
 // Three wave-uniform shortcuts, all invisible in the results: a group of calls
 // none of whose senders is faulty in a trial of the word is not drawn (a loyal
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kKingThreads) void k_king(uint32_t n, uint32_t m, u
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t i = lane & 31u, sl = lane >> 5;
     KingWave& s = lds[wv];
-    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
+    const uint32_t all = general_mask(n);
     const uint32_t npairs = (n + 1) / 2;
     // the update's two thresholds: c1 >= S -> attack, c1 <= n - S -> retreat, else the king
     const uint32_t S = (n + 2 * m) / 2 + 1, Tmaj = n / 2 + 1;
@@ -137,22 +137,17 @@ __global__ __launch_bounds__(kKingThreads) void k_king(uint32_t n, uint32_t m, u
     for (uint64_t w = gwave; w < words; w += nwaves) {
         const uint64_t t = w * 64 + lane, gw = (first_trial >> 6) + w;
         const bool live = t < batch;
-        uint32_t fm = 0, oc = 0;
-        if (live) {
-            if (gen.faulty_mode == 0) fm = faulty[t];
-            if (gen.order_mode == 0) oc = order[t];
-            if constexpr (GEN) gen_trial(n, seed, gen, first_trial + t, fm, oc);
-        }
-        fm &= all;
-        // planes of the word (a trial past the batch: nobody faulty, retreat)
+        uint32_t fm, oc;
+        trial_inputs<GEN>(live, n, all, seed, gen, first_trial, t, faulty, order, fm, oc);
+        // planes of the word
         const uint64_t OB = __ballot(oc == 1);
         uint64_t myF = 0, F0 = 0;
         for (uint32_t g = 0; g < n; ++g) {
-            const uint64_t pl = __ballot(((fm >> g) & 1u) != 0);
+            const uint64_t pl = faulty_plane(fm, g);
             if (g == 0) F0 = pl;
             if (i == g) myF = pl;
         }
-        king_wave_sync();  // the previous word's epilogue has read pref
+        wave_sync();  // the previous word's epilogue has read pref
         if (lane < 32) s.F[lane] = myF;
         // round 0: the commander sends
         uint64_t pref = OB;
@@ -164,9 +159,9 @@ __global__ __launch_bounds__(kKingThreads) void k_king(uint32_t n, uint32_t m, u
         uint32_t st = 255;  // settled so far (lane = trial)
         if (settled && king_agree(s, lane, n, pref, myF)) st = 0;
         for (uint32_t p = 1; p <= phases; ++p) {
-            king_wave_sync();
+            wave_sync();
             if (lane < 32) s.pref[lane] = pref;
-            king_wave_sync();
+            wave_sync();
             // exchange round q = 2p - 1
             Count<kKingPartPlanes> tally;
             for (uint32_t v0 = 0; v0 < npairs; v0 += 8) {
@@ -183,7 +178,7 @@ __global__ __launch_bounds__(kKingThreads) void k_king(uint32_t n, uint32_t m, u
             // merge the two slices' tallies: c1 of general i, six planes
 #pragma unroll
             for (int b = 0; b < kKingPartPlanes; ++b) s.part[b][lane] = tally.c[b];
-            king_wave_sync();
+            wave_sync();
             Count<kKingPartPlanes + 1> c1;
             {
                 uint64_t carry = 0;
@@ -199,7 +194,7 @@ __global__ __launch_bounds__(kKingThreads) void k_king(uint32_t n, uint32_t m, u
             // king round q = 2p: general k = p - 1 shows its majority
             const uint32_t k = p - 1;
             if (lane == k) s.kmaj = c1.ge(Tmaj);
-            king_wave_sync();
+            wave_sync();
             const uint64_t kmaj = s.kmaj, Fk = s.F[k];
             uint64_t km = kmaj;
             if (__ballot(Fk != 0) != 0) {
@@ -214,15 +209,11 @@ __global__ __launch_bounds__(kKingThreads) void k_king(uint32_t n, uint32_t m, u
             }
         }
         // epilogue, lane = trial: decisions, quorum, flags
-        king_wave_sync();
+        wave_sync();
         if (lane < 32) s.pref[lane] = pref;
-        king_wave_sync();
+        wave_sync();
         uint32_t A = 0;
-        {
-            const uint32_t half = lane >> 5, sh = lane & 31;
-            for (uint32_t r = 1; r < n; ++r)
-                A |= ((reinterpret_cast<const uint32_t*>(&s.pref[r])[half] >> sh) & 1u) << r;
-        }
+        for (uint32_t r = 1; r < n; ++r) A |= lane_bit(&s.pref[r], lane) << r;
         TrialResult res = trial_result(n, 0, fm, oc, A, 0);
         // in-bound is Phase King's: |F| <= m and n > 4m
         res.out = (res.out & ~32u) | ((res.nf <= m && n > 4 * m) ? 32u : 0u);
@@ -231,7 +222,7 @@ __global__ __launch_bounds__(kKingThreads) void k_king(uint32_t n, uint32_t m, u
             if (outcome) outcome[t] = (uint8_t)res.out;
             if (settled) settled[t] = (uint8_t)st;
         }
-        king_counts_add(live, res, lane, mine);
+        lane_counts_add<false>(live, res, lane, mine);
     }
     sink_counters(lane, mine, gwave, nwaves, counters, sk);
 }

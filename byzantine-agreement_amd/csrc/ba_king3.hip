@@ -22,7 +22,8 @@
 //   part[p][l]      plane p of lane l's tally, read back by lane l ^ 32; the two
 //                   tallies of the propose round pass through it one after the other
 //   kx, agr         the king's x plane; the loyal attack / retreat holders of `settled`
-// The wave helpers are ba_king_common.hpp's, shared with k_king.
+// The King helpers are ba_king_common.hpp's, shared with k_king; the wave
+// helpers ba_wave_proto.hpp's.
 //
 // The three wave-uniform shortcuts of k_king hold here too, invisible in the
 // results: a group of calls none of whose senders is faulty in a trial of the
@@ -154,10 +155,10 @@ __device__ __forceinline__ void king3_round(const King3Wave& s, uint32_t i, uint
 // The two slices' tallies of general i merged through s.part: six planes, up to 32.
 __device__ __forceinline__ Count<kKing3PartPlanes + 1> king3_merge(King3Wave& s, uint32_t lane,
                                                                    const Tally3& tally) {
-    king_wave_sync();  // the previous merge has read part
+    wave_sync();  // the previous merge has read part
 #pragma unroll
     for (int b = 0; b < kKing3PartPlanes; ++b) s.part[b][lane] = tally.c[b];
-    king_wave_sync();
+    wave_sync();
     Count<kKing3PartPlanes + 1> c;
     uint64_t carry = 0;
 #pragma unroll
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(kKing3Threads) void k_king3(uint32_t n, uint32_t m,
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t i = lane & 31u, sl = lane >> 5;
     King3Wave& s = lds[wv];
-    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
+    const uint32_t all = general_mask(n);
     const uint32_t npairs = (n + 1) / 2;
     // the thresholds, compared as signed integers: n - m <= 0 always holds
     // (Count::ge(0) is all ones); m + 1 <= 11
@@ -195,22 +196,17 @@ __global__ __launch_bounds__(kKing3Threads) void k_king3(uint32_t n, uint32_t m,
     for (uint64_t w = gwave; w < words; w += nwaves) {
         const uint64_t t = w * 64 + lane, gw = (first_trial >> 6) + w;
         const bool live = t < batch;
-        uint32_t fm = 0, oc = 0;
-        if (live) {
-            if (gen.faulty_mode == 0) fm = faulty[t];
-            if (gen.order_mode == 0) oc = order[t];
-            if constexpr (GEN) gen_trial(n, seed, gen, first_trial + t, fm, oc);
-        }
-        fm &= all;
-        // planes of the word (a trial past the batch: nobody faulty, retreat)
+        uint32_t fm, oc;
+        trial_inputs<GEN>(live, n, all, seed, gen, first_trial, t, faulty, order, fm, oc);
+        // planes of the word
         const uint64_t OB = __ballot(oc == 1);
         uint64_t myF = 0, F0 = 0;
         for (uint32_t g = 0; g < n; ++g) {
-            const uint64_t pl = __ballot(((fm >> g) & 1u) != 0);
+            const uint64_t pl = faulty_plane(fm, g);
             if (g == 0) F0 = pl;
             if (i == g) myF = pl;
         }
-        king_wave_sync();  // the previous word's epilogue has read pref
+        wave_sync();  // the previous word's epilogue has read pref
         if (lane < 32) s.F[lane] = myF;
         // round 0: the commander sends
         uint64_t pref = OB;
@@ -222,9 +218,9 @@ __global__ __launch_bounds__(kKing3Threads) void k_king3(uint32_t n, uint32_t m,
         uint32_t st = 255;  // settled so far (lane = trial)
         if (settled && king_agree(s, lane, n, pref, myF)) st = 0;
         for (uint32_t p = 1; p <= phases; ++p) {
-            king_wave_sync();
+            wave_sync();
             if (lane < 32) s.pref[lane] = pref;
-            king_wave_sync();
+            wave_sync();
             // value round q = 3p - 2
             uint64_t A, R;
             {
@@ -239,7 +235,7 @@ __global__ __launch_bounds__(kKing3Threads) void k_king3(uint32_t n, uint32_t m,
                 s.pa[lane] = A;
                 s.pr[lane] = R;
             }
-            king_wave_sync();
+            wave_sync();
             // propose round q = 3p - 1
             uint64_t x, sure;
             {
@@ -255,7 +251,7 @@ __global__ __launch_bounds__(kKing3Threads) void k_king3(uint32_t n, uint32_t m,
             // king round q = 3p: general k = p - 1 shows its x
             const uint32_t k = p - 1;
             if (lane == k) s.kx = x;
-            king_wave_sync();
+            wave_sync();
             const uint64_t kx = s.kx, Fk = s.F[k];
             uint64_t km = kx;
             if (__ballot(Fk != 0) != 0) {
@@ -270,15 +266,11 @@ __global__ __launch_bounds__(kKing3Threads) void k_king3(uint32_t n, uint32_t m,
             }
         }
         // epilogue, lane = trial: decisions, quorum, flags
-        king_wave_sync();
+        wave_sync();
         if (lane < 32) s.pref[lane] = pref;
-        king_wave_sync();
+        wave_sync();
         uint32_t Adec = 0;
-        {
-            const uint32_t half = lane >> 5, sh = lane & 31;
-            for (uint32_t r = 1; r < n; ++r)
-                Adec |= ((reinterpret_cast<const uint32_t*>(&s.pref[r])[half] >> sh) & 1u) << r;
-        }
+        for (uint32_t r = 1; r < n; ++r) Adec |= lane_bit(&s.pref[r], lane) << r;
         TrialResult res = trial_result(n, 0, fm, oc, Adec, 0);
         // in-bound is this protocol's: |F| <= m and n > 3m
         res.out = (res.out & ~32u) | ((res.nf <= m && n > 3 * m) ? 32u : 0u);
@@ -287,7 +279,7 @@ __global__ __launch_bounds__(kKing3Threads) void k_king3(uint32_t n, uint32_t m,
             if (outcome) outcome[t] = (uint8_t)res.out;
             if (settled) settled[t] = (uint8_t)st;
         }
-        king_counts_add(live, res, lane, mine);
+        lane_counts_add<false>(live, res, lane, mine);
     }
     sink_counters(lane, mine, gwave, nwaves, counters, sk);
 }

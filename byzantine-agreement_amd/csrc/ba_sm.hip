@@ -15,7 +15,7 @@
 //                       fresh_v[j] & (~F[j] | coin_v) into it (64-bit LDS atomic OR)
 //   has[v][r]           final V planes for the lane = trial epilogue
 // The DS instructions of one wave execute in issue order, so between the
-// phases only the compiler has to be held (wave_sync).
+// phases only the compiler has to be held (wave_sync, ba_wave_proto.hpp).
 //
 // One Philox call (ctr word 1 = 64 + k) yields the retreat and attack coins of
 // one pair for the 64 trials; a lane with several pairs groups up to four calls
@@ -23,7 +23,7 @@
 // a round in which no lieutenant holds a fresh value ends the relay, and a
 // group of pairs none of whose senders is both faulty and fresh in some trial
 // draws no coins (a loyal sender's coin is never read).
-#include "ba_engine.hpp"
+#include "ba_wave_proto.hpp"
 
 namespace ba {
 
@@ -37,80 +37,6 @@ struct SmWave {
     uint64_t recv[2][kMaxN];
     uint64_t has[2][kMaxN];
 };
-
-// orders this wave's LDS accesses for the compiler (no instruction: one wave's
-// DS operations complete in order)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void lds_or(uint64_t* p, uint64_t v) {
-    (void)__hip_atomic_fetch_or((unsigned long long*)p, (unsigned long long)v, __ATOMIC_RELAXED,
-                                __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// §2.4's epilogue with the SM rules of §6: decisions are never undefined and
-// in-bound is |F| <= m (the parameter m, no condition on n).  A: lieutenant
-// bitmask (bit r, r = 1..n-1) of attack decisions.
-__device__ __forceinline__ TrialResult sm_trial_result(uint32_t n, uint32_t m, uint32_t fm,
-                                                       uint32_t oc, uint32_t A) {
-    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
-    const uint32_t lts = all & ~1u;
-    fm &= all;
-    A &= lts;
-    const uint32_t nA = __popc(A), nR = (n - 1) - nA;
-    const uint32_t na = nA + (oc == 1), nu = (oc == 2), nr = nR + (oc == 0);
-    const uint32_t total = na + nr + nu;
-    uint32_t needed = 2 * ((total - 1) / 3) + 1;
-    if (total <= 3) needed = total - 1;
-    if (total == 1) needed = 1;
-    const uint32_t q = needed <= nr ? 0u : (needed <= na ? 1u : 2u);  // retreat first
-    const uint32_t loyal = lts & ~fm;
-    const uint32_t la = A & loyal, lr = loyal & ~A;
-    const uint32_t agree = ((la != 0) + (lr != 0)) <= 1;
-    const uint32_t appl = (fm & 1u) == 0 ? 1u : 0u;
-    const uint32_t okA = la == loyal ? 1u : 0u, okR = lr == loyal ? 1u : 0u;
-    const uint32_t valid = appl & (oc == 1 ? okA : okR);
-    const uint32_t nf = __popc(fm);
-    const uint32_t inb = nf <= m ? 1u : 0u;
-    TrialResult r;
-    r.dec = part1by1(A >> 1);
-    r.out = q | agree << 2 | appl << 3 | valid << 4 | inb << 5;
-    r.nU = 0;
-    r.nf = nf;
-    r.nA = nA;
-    return r;
-}
-
-// Wave totals of one word's run counters added into `mine` (lane c holds
-// counter c): flags by ballot + popcount, the small integers bit-sliced
-// (faulty_total up to 32 per trial: six planes).
-__device__ __forceinline__ void sm_counts_add(bool live, const TrialResult& r, uint32_t lane,
-                                              uint64_t& mine) {
-    const uint32_t o = r.out, q = o & 3;
-    const bool agree = (o >> 2) & 1, appl = (o >> 3) & 1, valid = (o >> 4) & 1, inb = (o >> 5) & 1;
-    uint32_t c[C_NUM];
-    c[C_TRIALS] = __popcll(__ballot(live));
-    c[C_AGREE] = __popcll(__ballot(live && agree));
-    c[C_VAPPL] = __popcll(__ballot(live && appl));
-    c[C_VALID] = __popcll(__ballot(live && valid));
-    c[C_QR] = __popcll(__ballot(live && q == 0));
-    c[C_QA] = __popcll(__ballot(live && q == 1));
-    c[C_QU] = __popcll(__ballot(live && q == 2));
-    c[C_INB] = __popcll(__ballot(live && inb));
-    c[C_VIOL] = __popcll(__ballot(live && inb && (!agree || (appl && !valid))));
-    c[C_UNDEF] = c[C_FTOT] = c[C_ATT] = 0;
-#pragma unroll
-    for (int b = 0; b < 6; ++b) {
-        c[C_FTOT] += (uint32_t)__popcll(__ballot(live && ((r.nf >> b) & 1u))) << b;
-        c[C_ATT] += (uint32_t)__popcll(__ballot(live && ((r.nA >> b) & 1u))) << b;
-    }
-#pragma unroll
-    for (int i = 0; i < C_NUM; ++i)
-        if (lane == (uint32_t)i) mine += c[i];
-}
 
 // One group of G relay passes of round k: lane l takes pairs base + 64 g + l.
 template <int G>
@@ -176,7 +102,7 @@ __global__ __launch_bounds__(kSmThreads) void k_sm(uint32_t n, uint32_t m, uint3
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     SmWave& s = lds[wv];
     const uint32_t L = n - 1, P = L * (L - 1);  // n = 1: L = 0, P = 0
-    const uint32_t all = n >= 32 ? 0xFFFFFFFFu : ((1u << n) - 1u);
+    const uint32_t all = general_mask(n);
     const uint64_t words = (batch + 63) / 64;
     const uint32_t nwaves = gridDim.x * (kSmThreads / 64), gwave = blockIdx.x * (kSmThreads / 64) + wv;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -184,17 +110,12 @@ __global__ __launch_bounds__(kSmThreads) void k_sm(uint32_t n, uint32_t m, uint3
     for (uint64_t w = gwave; w < words; w += nwaves) {
         const uint64_t i = w * 64 + lane, gw = (first_trial >> 6) + w;
         const bool live = i < batch;
-        uint32_t fm = 0, oc = 0;
-        if (live) {
-            if (gen.faulty_mode == 0) fm = faulty[i];
-            if (gen.order_mode == 0) oc = order[i];
-            if constexpr (GEN) gen_trial(n, seed, gen, first_trial + i, fm, oc);
-        }
-        fm &= all;
+        uint32_t fm, oc;
+        trial_inputs<GEN>(live, n, all, seed, gen, first_trial, i, faulty, order, fm, oc);
         // planes of the word
         const uint64_t VAL = __ballot(live), F0 = __ballot((fm & 1u) != 0), OB = __ballot(oc == 1);
         for (uint32_t g = 1; g < n; ++g) {
-            const uint64_t pl = __ballot(((fm >> g) & 1u) != 0);
+            const uint64_t pl = faulty_plane(fm, g);
             if (lane == g - 1) s.F[g - 1] = pl;
         }
         // round 0: the commander sends; a faulty one signs each value by a coin
@@ -243,20 +164,20 @@ __global__ __launch_bounds__(kSmThreads) void k_sm(uint32_t n, uint32_t m, uint3
         }
         wave_sync();
         uint32_t vR = 0, vA = 0;
-        {
-            const uint32_t half = lane >> 5, sh = lane & 31;
-            for (uint32_t r = 0; r < L; ++r) {
-                vR |= ((reinterpret_cast<const uint32_t*>(&s.has[0][r])[half] >> sh) & 1u) << r;
-                vA |= ((reinterpret_cast<const uint32_t*>(&s.has[1][r])[half] >> sh) & 1u) << r;
-            }
+        for (uint32_t r = 0; r < L; ++r) {
+            vR |= lane_bit(&s.has[0][r], lane) << r;
+            vA |= lane_bit(&s.has[1][r], lane) << r;
         }
-        const TrialResult res = sm_trial_result(n, m, fm, oc, (vA & ~vR) << 1);  // V = {attack}
+        // §2.4's epilogue with the SM rules of §6: decisions are never undefined
+        // (attack where V = {attack}) and in-bound is |F| <= m, no condition on n
+        TrialResult res = trial_result(n, 0, fm, oc, (vA & ~vR) << 1, 0);
+        res.out = (res.out & ~32u) | (res.nf <= m ? 32u : 0u);
         if (live) {
             if (decisions) decisions[i] = res.dec;
             if (outcome) outcome[i] = (uint8_t)res.out;
             if (vsets) vsets[i] = part1by1(vA) | part1by1(vR) << 1;
         }
-        sm_counts_add(live, res, lane, mine);
+        lane_counts_add<false>(live, res, lane, mine);
     }
     sink_counters(lane, mine, gwave, nwaves, counters, sk);
 }

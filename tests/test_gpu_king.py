@@ -194,6 +194,22 @@ def test_host_entry_chunks(engine, monkeypatch):
     check(one, model(10, 3, K.KING_COIN, B, SEEDS[0], O.FAULTY_RANDOM, 10, O.ORDER_RANDOM), "one chunk")
 
 
+def test_host_entry_settled_without_outcome(engine, monkeypatch):
+    """The extra plane alone through the chunked host entry: `settled` rides behind the
+    outcome bytes in one staging buffer and is asked for without them (64-trial chunks,
+    a partial last word)."""
+    from ba_amd import lib as L
+    n, m, b = 4, 1, 130
+    monkeypatch.setenv("BA_KING_HOST_CHUNK", "64")
+    res = engine.run_king(n, m, b, K.KING_COIN, seed=SEEDS[0], faulty_mode=L.FAULTY_RANDOM, f=n,
+                          order_mode=L.ORDER_RANDOM, want_decisions=False, want_outcome=False,
+                          want_settled=True)
+    ref = model(n, m, K.KING_COIN, b, SEEDS[0], O.FAULTY_RANDOM, n, O.ORDER_RANDOM)
+    assert res.decisions is None and res.outcome is None
+    same(res.settled, ref[2], "settled")
+    assert {k: res.counters[k] for k in ref[3]} == ref[3]
+
+
 def test_staged_inputs_equal_in_kernel_draws_and_optional_outputs(engine):
     """ba_gen_inputs_device + GIVEN == drawing in the kernel; the decisions, outcome
     and settled pointers are each optional, in every combination, and an absent

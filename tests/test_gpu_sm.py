@@ -183,6 +183,22 @@ def test_host_entry_chunks(engine, monkeypatch):
     check(one, model(10, 3, B, SEEDS[0], O.FAULTY_RANDOM, 10, O.ORDER_RANDOM), "one chunk")
 
 
+def test_host_entry_vsets_without_decisions(engine, monkeypatch):
+    """The extra plane alone through the chunked host entry: the V sets ride behind the
+    decisions in one staging buffer and are asked for without them (64-trial chunks, a
+    partial last word)."""
+    from ba_amd import lib as L
+    n, m, b = 4, 1, 130
+    monkeypatch.setenv("BA_SM_HOST_CHUNK", "64")
+    res = engine.run_sm(n, m, b, seed=SEEDS[0], faulty_mode=L.FAULTY_RANDOM, f=n,
+                        order_mode=L.ORDER_RANDOM, want_decisions=False, want_outcome=False,
+                        want_vsets=True)
+    ref = model(n, m, b, SEEDS[0], O.FAULTY_RANDOM, n, O.ORDER_RANDOM)
+    assert res.decisions is None and res.outcome is None
+    same(res.vsets, ref[2], "vsets")
+    assert {k: res.counters[k] for k in ref[3]} == ref[3]
+
+
 def test_staged_inputs_equal_in_kernel_draws_and_optional_outputs(engine):
     """ba_gen_inputs_device + GIVEN == drawing in the kernel; the decisions, outcome
     and vsets pointers are each optional, in every combination."""
