@@ -52,8 +52,11 @@ EXPORTS = ["ba_version", "ba_device_count", "ba_ctx_create", "ba_ctx_destroy", "
            "ba_enum_bits", "ba_enum_slots", "ba_enum_run", "ba_enum_run_device",
            "ba_king_run_trials", "ba_king_run_trials_device", "ba_king_coin_calls",
            "ba_king_phases", "ba_king3_run_trials", "ba_king3_run_trials_device",
-           "ba_king3_coin_calls", "ba_king3_phases"]
-ENUM_MAX_BITS = 48  # BA_ENUM_MAX_BITS (docs/SEMANTICS.md §8)
+           "ba_king3_coin_calls", "ba_king3_phases",
+           "ba_kenum_bits", "ba_kenum_slots", "ba_kenum_run", "ba_kenum_run_device"]
+KENUM_KING, KENUM_KING3 = 0, 1  # the protocol of run_kenum (docs/SEMANTICS.md §11)
+KENUM_MAX_N = 16  # k_kenum is built for n = 1..16
+ENUM_MAX_BITS = 48  # BA_ENUM_MAX_BITS (docs/SEMANTICS.md §8, §11)
 NO_WITNESS = (1 << 64) - 1
 PROBE_BLOCKS = 2048  # BA_PROBE_BLOCKS
 
@@ -206,6 +209,13 @@ def load(path: str | None = None):
     lib.ba_king3_coin_calls.restype = u64
     lib.ba_king3_phases.argtypes = [u32, u32]
     lib.ba_king3_phases.restype = u32
+    lib.ba_kenum_bits.argtypes = [u32, u32, u32, u32]
+    lib.ba_kenum_bits.restype = u32
+    lib.ba_kenum_slots.argtypes = [u32, u32, u32, u32, vp, vp, vp, vp, u32]
+    lib.ba_kenum_run.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u32, u64, vp, vp,
+                                 ctypes.POINTER(Counters), ctypes.POINTER(u64)]
+    lib.ba_kenum_run_device.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u32, u64, vp, vp, vp,
+                                        vp, vp]
     if lib.ba_version() != ABI_VERSION:
         raise RuntimeError(f"libba_hip ABI {lib.ba_version()} != {ABI_VERSION}")
     if path is None:
@@ -449,6 +459,38 @@ class Engine:
         graph it raises BAError(ENOTSUP) and queues nothing."""
         _check(self.lib, self.lib.ba_enum_run_device(
             self.handle, ctypes.byref(params), faulty_mask & 0xFFFFFFFF, order, count,
+            d_decisions or None, d_outcome or None, d_counters or None, d_witness or None,
+            stream or None))
+
+    def run_kenum(self, proto, n, m, faulty_mask, order, first=0, count=None, want_decisions=False,
+                  want_outcome=False, lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN,
+                  order_mode=ORDER_GIVEN, engine=ENGINE_AUTO) -> RunResult:
+        """Walk the traitor strategies S in [first, first + count) of the Phase King
+        (KENUM_KING) or KING3 (KENUM_KING3) case (n, m, faulty_mask, order)
+        (docs/SEMANTICS.md §11; ba_kenum_run); count=None: up to the end of the space,
+        2^kenum_bits.  The result's `witness` is the smallest violating S of the range
+        (decode_kstrategy reads it), None when no strategy violates."""
+        if count is None:
+            b = kenum_bits(proto, n, m, faulty_mask)
+            count = max(0, (1 << b) - first) if b <= ENUM_MAX_BITS else 0  # above the cap: the call says so
+        dec = np.zeros(count, np.uint64) if want_decisions else None
+        out = np.zeros(count, np.uint8) if want_outcome else None
+        p = make_params(n, m, 0, lie_mode, faulty_mode, 0, order_mode, ATTACK, engine, first)
+        cnt, wit = Counters(), ctypes.c_uint64(NO_WITNESS)
+        _check(self.lib, self.lib.ba_kenum_run(self.handle, ctypes.byref(p), proto,
+                                               faulty_mask & 0xFFFFFFFF, order, count, _ptr(dec),
+                                               _ptr(out), ctypes.byref(cnt), ctypes.byref(wit)))
+        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])),
+                         witness=None if wit.value == NO_WITNESS else int(wit.value))
+
+    def run_kenum_device(self, params: Params, proto: int, faulty_mask: int, order: int, count: int,
+                         d_decisions=0, d_outcome=0, d_counters=0, d_witness=0, stream=0):
+        """Enqueue strategies [params.first_trial, + count) on device pointers
+        (ba_kenum_run_device); counters accumulated, the witness (uint64, set to NO_WITNESS
+        by the caller) min-accumulated.  Fully asynchronous: nothing is copied from the
+        host, so a stream that is capturing a graph takes the call."""
+        _check(self.lib, self.lib.ba_kenum_run_device(
+            self.handle, ctypes.byref(params), proto, faulty_mask & 0xFFFFFFFF, order, count,
             d_decisions or None, d_outcome or None, d_counters or None, d_witness or None,
             stream or None))
 
@@ -794,6 +836,68 @@ def encode_strategy(n: int, m: int, faulty_mask: int, values) -> int:
         if given[p] not in (0, 1):
             raise ValueError(f"value of path {p} is {given[p]!r}, not 0 or 1")
         S |= int(given[p]) << i
+    return S
+
+
+def kenum_bits(proto: int, n: int, m: int, faulty_mask: int) -> int:
+    """Free bits B of a Phase King / KING3 case's strategy space (ba_kenum_bits);
+    0xFFFFFFFF for a bad proto / n / m."""
+    return int(load().ba_kenum_bits(proto, n, m, faulty_mask & 0xFFFFFFFF))
+
+
+def kenum_slots(proto: int, n: int, m: int, faulty_mask: int) -> list:
+    """[(q, sender, recipient, part)] of free bits 0..B-1 (ba_kenum_slots): part is 0 for a
+    one-bit message, 0 / 1 for lo / hi of a KING3 proposal."""
+    lib = load()
+    b = kenum_bits(proto, n, m, faulty_mask)
+    cap = b if b != 0xFFFFFFFF else 0
+    arr = [np.zeros(max(cap, 1), np.uint32) for _ in range(4)]
+    got = lib.ba_kenum_slots(proto, n, m, faulty_mask & 0xFFFFFFFF, *(a.ctypes.data for a in arr), cap)
+    if got < 0:
+        raise BAError(got, lib.ba_last_error().decode())
+    return [tuple(int(a[i]) for a in arr) for i in range(got)]
+
+
+def decode_kstrategy(proto: int, n: int, m: int, faulty_mask: int, S: int) -> dict:
+    """{(q, sender, recipient): value} of the free messages under strategy S
+    (docs/SEMANTICS.md §11): 1 = attack / 0 = retreat; in KING3's propose round None is
+    no proposal (lo = 0, whatever hi is), else the value proposed."""
+    out = {}
+    for i, (q, j, r, part) in enumerate(kenum_slots(proto, n, m, faulty_mask)):
+        bit = (S >> i) & 1
+        if part == 0:
+            out[(q, j, r)] = bit  # a proposal's lo for now
+        else:
+            out[(q, j, r)] = bit if out[(q, j, r)] else None
+    return out
+
+
+def encode_kstrategy(proto: int, n: int, m: int, faulty_mask: int, values) -> int:
+    """The strategy index S of `{(q, sender, recipient): value}`, the inverse of
+    decode_kstrategy: `values` gives 0 / 1 (or None, in KING3's propose round only) for
+    exactly the free messages of the case.  No proposal is coded (lo, hi) = (0, 0), the
+    smaller of its two codes, so encode(decode(S)) clears the hi bit of a withheld
+    proposal and is S otherwise.  A missing message, one that is not free and a value
+    that the round cannot carry raise ValueError."""
+    given = {tuple(k): v for k, v in dict(values).items()}
+    slots = kenum_slots(proto, n, m, faulty_mask)
+    msgs = {(q, j, r) for q, j, r, _ in slots}
+    missing = sorted(msgs - set(given))
+    extra = sorted(set(given) - msgs)
+    if missing or extra:
+        raise ValueError(f"strategy of (proto={proto}, n={n}, m={m}, F={faulty_mask:#b}) has {len(msgs)} "
+                         f"free messages: missing {missing[:4]}, not free {extra[:4]}")
+    two = {(q, j, r) for q, j, r, part in slots if part == 1}
+    S = 0
+    for i, (q, j, r, part) in enumerate(slots):
+        v = given[(q, j, r)]
+        if v not in ((0, 1, None) if (q, j, r) in two else (0, 1)):
+            raise ValueError(f"value of message {(q, j, r)} is {v!r}")
+        if (q, j, r) in two:
+            bit = (0 if v is None else 1) if part == 0 else (0 if v is None else int(v))
+        else:
+            bit = int(v)
+        S |= bit << i
     return S
 
 

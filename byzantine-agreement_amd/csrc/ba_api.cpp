@@ -1575,6 +1575,157 @@ extern "C" int ba_enum_run(ba_ctx* ctx, const ba_params* p, uint32_t faulty_mask
     return rc;
 }
 
+// ---------------------------------------------------------------------------
+// Phase King and KING3 against every traitor strategy of one case
+// (docs/SEMANTICS.md §11; ba_kenum.hip)
+// ---------------------------------------------------------------------------
+// The numbers of a case that its bit count and slot list are made of; P = 0: bad
+// proto, n or m.
+struct KenumShape {
+    uint32_t P = 0, F = 0, nf = 0, ell = 0, fK = 0;
+};
+
+static KenumShape kenum_shape(uint32_t proto, uint32_t n, uint32_t m, uint32_t faulty_mask) {
+    KenumShape s;
+    if (proto > BA_KENUM_KING3) return s;
+    s.P = proto == BA_KENUM_KING ? ba_king_phases(n, m) : ba_king3_phases(n, m);
+    if (s.P == 0) return s;
+    s.F = faulty_mask & general_mask(n);
+    s.nf = (uint32_t)__builtin_popcount(s.F);
+    s.ell = n - s.nf;
+    s.fK = (uint32_t)__builtin_popcount(s.F & general_mask(s.P));  // the kings are generals 0..P-1
+    return s;
+}
+
+// B = [F_0] l + r P |F| l + fK l, r = 1 (KING) or 3 (KING3: value, and two bits per proposal)
+extern "C" uint32_t ba_kenum_bits(uint32_t proto, uint32_t n, uint32_t m, uint32_t faulty_mask) {
+    const KenumShape s = kenum_shape(proto, n, m, faulty_mask);
+    if (s.P == 0) return 0xFFFFFFFFu;
+    const uint64_t per_phase = proto == BA_KENUM_KING ? 1 : 3;
+    const uint64_t B = (uint64_t)(s.F & 1u) * s.ell + per_phase * s.P * s.nf * s.ell + (uint64_t)s.fK * s.ell;
+    return B > kEnumBitsSaturated ? kEnumBitsSaturated : (uint32_t)B;
+}
+
+extern "C" int ba_kenum_slots(uint32_t proto, uint32_t n, uint32_t m, uint32_t faulty_mask,
+                              uint32_t* q, uint32_t* sender, uint32_t* recipient, uint32_t* part,
+                              uint32_t cap) {
+    const KenumShape s = kenum_shape(proto, n, m, faulty_mask);
+    if (s.P == 0) return fail(BA_EINVAL, "proto=%u n=%u m=%u", proto, n, m);
+    const uint32_t B = ba_kenum_bits(proto, n, m, faulty_mask);
+    if (B > cap) return fail(BA_EINVAL, "cap=%u < %u free bits", cap, B);
+    if (B && (!q || !sender || !recipient || !part))
+        return fail(BA_EINVAL, "q, sender, recipient and part are required");
+    uint32_t bit = 0;
+    // the free messages of round qq from sender j, in recipient order; parts bits each
+    auto round_of = [&](uint32_t qq, uint32_t j, uint32_t parts) {
+        if (!((s.F >> j) & 1u)) return;
+        for (uint32_t i = 0; i < n; ++i) {
+            if ((s.F >> i) & 1u) continue;
+            for (uint32_t h = 0; h < parts; ++h, ++bit)
+                q[bit] = qq, sender[bit] = j, recipient[bit] = i, part[bit] = h;
+        }
+    };
+    const uint32_t per = proto == BA_KENUM_KING ? 2 : 3;  // rounds of a phase
+    round_of(0, 0, 1);
+    for (uint32_t p = 1; p <= s.P; ++p) {
+        for (uint32_t j = 0; j < n; ++j) round_of(per * p - (per - 1), j, 1);
+        if (proto == BA_KENUM_KING3)
+            for (uint32_t j = 0; j < n; ++j) round_of(3 * p - 1, j, 2);
+        round_of(per * p, p - 1, 1);
+    }
+    if (bit != B) return fail(BA_EINVAL, "internal: %u free bits listed, formula %u", bit, B);
+    return (int)B;
+}
+
+static int validate_kenum(const ba_params* p, uint32_t proto, uint32_t faulty_mask, uint32_t order,
+                          uint64_t batch, KenumCase& g) {
+    if (proto > BA_KENUM_KING3) return fail(BA_EINVAL, "proto=%u", proto);
+    int rc = validate_protocol(p, batch, true, true, "the King enumeration",
+                               proto == BA_KENUM_KING ? (uint32_t)BA_MAX_DEPTH : kKing3MaxM);
+    if (rc != BA_OK) return rc;
+    if (p->faulty_mode != BA_FAULTY_GIVEN || p->order_mode != BA_ORDER_GIVEN)
+        return fail(BA_EINVAL, "faulty_mode=%u order_mode=%u: one given faulty set and order per call "
+                    "(BA_FAULTY_GIVEN, BA_ORDER_GIVEN)", p->faulty_mode, p->order_mode);
+    if (order > BA_OTHER) return fail(BA_EINVAL, "order=%u", order);
+    if (p->n > kKenumMaxN)
+        return fail(BA_ETOOBIG, "n=%u > %u: k_kenum keeps one plane per general in registers", p->n,
+                    kKenumMaxN);
+    const uint32_t B = ba_kenum_bits(proto, p->n, p->m, faulty_mask);
+    if (B > BA_ENUM_MAX_BITS)
+        return fail(BA_ETOOBIG, "proto=%u n=%u m=%u faulty_mask=0x%x: %u free bits > %d", proto, p->n,
+                    p->m, faulty_mask, B, BA_ENUM_MAX_BITS);
+    const uint64_t space = 1ull << B;
+    if (p->first_trial > space || batch > space - p->first_trial)
+        return fail(BA_EINVAL, "strategies [%llu, %llu + %llu) reach past 2^%u",
+                    (unsigned long long)p->first_trial, (unsigned long long)p->first_trial,
+                    (unsigned long long)batch, B);
+    const KenumShape s = kenum_shape(proto, p->n, p->m, faulty_mask);
+    g.proto = proto, g.m = p->m, g.phases = s.P, g.fmask = s.F, g.order = order;
+    return BA_OK;
+}
+
+// Strategies [first, first + batch) of a case, kEnumLaunchMax per launch (the
+// sink's per-launch sums, at most 15 decisions per strategy, stay below 2^48).
+static int kenum_launch_range(ba_ctx* ctx, const ba_params* p, const KenumCase& g, uint64_t first,
+                              uint64_t batch, uint64_t* d_decisions, uint8_t* d_outcome,
+                              uint64_t* d_counters, uint64_t* d_witness, void* stream) {
+    ba_params q = *p;
+    for (uint64_t t0 = 0; t0 < batch; t0 += kEnumLaunchMax) {
+        const uint64_t nt = batch - t0 < kEnumLaunchMax ? batch - t0 : kEnumLaunchMax;
+        q.first_trial = first + t0;
+        const RunArgs a = make_args(ctx, &q, nt, nullptr, nullptr, nullptr, nullptr,
+                                    d_decisions ? d_decisions + t0 : nullptr,
+                                    d_outcome ? d_outcome + t0 : nullptr, d_counters, stream);
+        HIP_TRY(launch_kenum(a, g, d_witness));
+    }
+    return BA_OK;
+}
+
+// Nothing is copied from the host: fully asynchronous, and a stream that is
+// capturing a graph takes it.
+extern "C" int ba_kenum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t proto,
+                                   uint32_t faulty_mask, uint32_t order, uint64_t batch,
+                                   uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_counters,
+                                   uint64_t* d_witness, void* stream) {
+    return ordered(ctx, stream, [&] {
+        KenumCase g{};
+        int rc = validate_kenum(p, proto, faulty_mask, order, batch, g);
+        if (rc != BA_OK) return rc;
+        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
+        if (batch == 0) return BA_OK;
+        return kenum_launch_range(ctx, p, g, p->first_trial, batch, d_decisions, d_outcome, d_counters,
+                                  d_witness, stream);
+    });
+}
+
+// Host entry: host_run with no inputs to copy; counters only: one chunk, chunks of
+// kHostChunk strategies when a per-trial output is asked for (the witness
+// min-accumulates across them on the device, in the word after the counters).
+extern "C" int ba_kenum_run(ba_ctx* ctx, const ba_params* p, uint32_t proto, uint32_t faulty_mask,
+                            uint32_t order, uint64_t batch, uint64_t* decisions, uint8_t* outcome,
+                            ba_counters* counters, uint64_t* witness) {
+    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
+    KenumCase g{};
+    int rc = validate_kenum(p, proto, faulty_mask, order, batch, g);
+    if (rc != BA_OK) return rc;
+    if (counters) memset(counters, 0, sizeof *counters);
+    if (witness) *witness = UINT64_MAX;
+    if (batch == 0) return BA_OK;
+    uint64_t wit = UINT64_MAX;
+    HostRun r;
+    r.decisions = decisions, r.outcome = outcome, r.counters = counters, r.tail = &wit;
+    r.chunk_env = "BA_KENUM_HOST_CHUNK";
+    r.chunk = (decisions || outcome) ? kHostChunk : batch;
+    r.queue = [&](const ba_params& q, uint64_t nt, const uint32_t*, const uint8_t*, uint64_t* d_dec,
+                  uint8_t* d_out, void*, uint64_t* d_cnt, hipStream_t st) {
+        return ba_kenum_run_device(ctx, &q, proto, faulty_mask, order, nt, d_dec, d_out, d_cnt,
+                                   d_cnt + BA_NCOUNTERS, st);
+    };
+    rc = host_run(ctx, p, batch, r);
+    if (rc == BA_OK && witness) *witness = wit;
+    return rc;
+}
+
 extern "C" int ba_split_votes_device(ba_ctx* ctx, const ba_params* p, uint64_t batch,
                                      uint32_t level, uint32_t u_begin, uint32_t u_end,
                                      const uint32_t* d_faulty, const uint8_t* d_order,

@@ -227,4 +227,16 @@ hipError_t launch_king(const RunArgs& a, uint32_t policy, uint32_t phases, uint8
 constexpr uint32_t kKing3MaxM = 10;
 hipError_t launch_king3(const RunArgs& a, uint32_t policy, uint32_t phases, uint8_t* settled);
 
+// Phase King and KING3 against every traitor strategy of one case (ba_kenum.hip,
+// docs/SEMANTICS.md §11): trial t is strategy S = t.  Everything the kernel needs
+// is in the case: no map, no upload.  n is a template parameter of k_kenum (the
+// generals' planes live in registers), instantiated for 1..kKenumMaxN.
+constexpr uint32_t kKenumMaxN = 16;
+struct KenumCase {
+    uint32_t proto;   // BA_KENUM_KING / BA_KENUM_KING3
+    uint32_t m, phases;
+    uint32_t fmask, order;  // fmask masked to n bits; order code 0..2
+};
+hipError_t launch_kenum(const RunArgs& a, const KenumCase& g, uint64_t* witness);
+
 }  // namespace ba

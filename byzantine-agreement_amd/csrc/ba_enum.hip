@@ -32,8 +32,9 @@
 // once per wave at the end and go through sink_counters.  The witness is the
 // wave's lowest violating S, one 64-bit atomic min per wave that found one.  The
 // lane = trial pick-out of decisions / outcome bytes runs only when asked for, on
-// one-wave blocks that keep the tile's decision planes in LDS.
-#include "ba_wave_proto.hpp"
+// one-wave blocks that keep the tile's decision planes in LDS.  enum_plane and
+// enum_wave_sum are ba_enum_common.hpp's, shared with k_kenum.
+#include "ba_enum_common.hpp"
 
 namespace ba {
 
@@ -50,22 +51,6 @@ struct EnumWalk {
     uint32_t L, r, fl;   // fl: bit j = lieutenant rank j is faulty
     uint32_t wlo, whi;   // this lane's word index w = S / 64
 };
-
-// plane of free bit i (uniform) in word w
-__device__ __forceinline__ uint64_t enum_plane(uint32_t i, uint32_t wlo, uint32_t whi) {
-    if (i < 6u) {
-        return i == 0u   ? 0xAAAAAAAAAAAAAAAAull
-               : i == 1u ? 0xCCCCCCCCCCCCCCCCull
-               : i == 2u ? 0xF0F0F0F0F0F0F0F0ull
-               : i == 3u ? 0xFF00FF00FF00FF00ull
-               : i == 4u ? 0xFFFF0000FFFF0000ull
-                         : 0xFFFFFFFF00000000ull;
-    }
-    const uint32_t sh = i - 6u;
-    const uint32_t h = sh < 32u ? wlo : whi;
-    const int32_t s = (int32_t)(h << (31u - (sh & 31u))) >> 31;  // -(bit sh of w)
-    return (uint64_t)(int64_t)s;
-}
 
 // value of the slot `rank` of level K whose sender is faulty: free or dead
 template <int K>
@@ -118,12 +103,6 @@ __device__ __forceinline__ uint64_t enum_resolve(const EnumWalk& c, uint64_t x, 
         if constexpr (K == 0) tie = (s & 1u) ? 0ull : (cnt.ge(s / 2u) & ~maj);
         return maj;
     }
-}
-
-__device__ __forceinline__ uint64_t enum_wave_sum(uint64_t x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-    return x;
 }
 
 template <int ME>

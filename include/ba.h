@@ -447,6 +447,68 @@ uint64_t ba_king3_coin_calls(uint32_t n, uint32_t m);  /* host only */
 /* P = min(m, n-1) + 1; 0 for n outside 1..32 or m > 10. */
 uint32_t ba_king3_phases(uint32_t n, uint32_t m);      /* host only */
 
+/* ---- Phase King and KING3 against every traitor strategy of one case -----------
+ * BA_KING_COIN and BA_KING_SPLIT are two adversaries; the theorems (agreement whenever
+ * n > 4m, n > 3m) speak of every choice of messages.  These entries walk all of them
+ * for one case (proto, n, m, faulty set, order) (docs/SEMANTICS.md §11; no ba.py
+ * analogue), as the ba_enum entries do for OM(m).  proto is BA_KENUM_KING (the
+ * rules of Phase King above) or BA_KENUM_KING3 (those of KING3); every general,
+ * faulty ones included, keeps a preference and runs the rules honestly.  A message
+ * from sender j to recipient i != j in round q (q = 0 the commander's send; Phase
+ * King: 2p-1 exchange, 2p king; KING3: 3p-2 value, 3p-1 propose, 3p king) is
+ *   truth   j is loyal;
+ *   dead    j and i are both faulty: retreat, and no proposal in KING3's propose
+ *           round (it cannot reach a loyal general's state);
+ *   free    j is faulty, i loyal: one free bit, 1 = attack; in KING3's propose round
+ *           two consecutive bits (lo, hi): lo = 0 is no proposal whatever hi is,
+ *           lo = 1 proposes hi.  A traitor may thus withhold a proposal, which the
+ *           coin and split adversaries never do; the codes (0,0) and (0,1) are one
+ *           strategy, so rates are rates over the coded space.
+ * Free bits are numbered in (q, sender, recipient) ascending order, lo before hi
+ * (ba_kenum_slots lists them).  With l = n - |F|, P the protocol's phase count and
+ * fK the faulty generals among the kings 0..P-1:
+ *   B = [0 in F] l + P |F| l + fK l      (BA_KENUM_KING)
+ *   B = [0 in F] l + 3 P |F| l + fK l    (BA_KENUM_KING3)
+ * Trial t of a call is strategy S = t: a call covers S in [p->first_trial,
+ * p->first_trial + batch), first_trial a multiple of 64, ending at or below 2^B
+ * (else BA_EINVAL).  p supplies n, m and first_trial; seed and f are unused.
+ * p->lie_mode must be BA_LIE_PHILOX (TABLE: BA_ENOTSUP), p->engine BA_ENGINE_AUTO,
+ * p->faulty_mode BA_FAULTY_GIVEN and p->order_mode BA_ORDER_GIVEN (else BA_EINVAL);
+ * proto > 1, order > BA_OTHER, m > 8 (KING) and m > 10 (KING3) are BA_EINVAL.
+ * B > BA_ENUM_MAX_BITS and n > 16 are BA_ETOOBIG: the kernel keeps one plane per
+ * general in registers and is built for n = 1..16.  The 48-bit cap already excludes
+ * nearly every larger case; what the n cap loses beyond it, all with n in 17..32:
+ * no traitor at all (B = 0); Phase King with m = 0 and up to three traitors (n <= 32,
+ * 26, 19 for one, two, three), m = 1 and one traitor (n <= 25), m = 2 and one
+ * traitor at n = 17; KING3 with m = 0 and one traitor at n = 17.
+ * decisions / outcome / counters: the layouts above, each protocol's own in-bound
+ * rule, faulty lieutenants deciding honestly on truth and dead inputs.  witness: the
+ * smallest S of the range that violates IC1 or (IC2 applicable) IC2, in bound or
+ * not, or 2^64 - 1 when none does.  batch = 0: BA_OK, zero counters, witness
+ * 2^64 - 1.  At most 2^40 strategies go into one launch.  Nothing is copied from
+ * host memory: ba_kenum_run_device is fully asynchronous and may be captured in a
+ * graph. */
+#define BA_KENUM_KING 0
+#define BA_KENUM_KING3 1
+/* B; host only.  0xFFFFFFFF for proto > 1, n outside 1..32 or m above the
+ * protocol's limit; saturates at 0xFFFFFFFE.  Not limited to n <= 16. */
+uint32_t ba_kenum_bits(uint32_t proto, uint32_t n, uint32_t m, uint32_t faulty_mask);
+/* bit i -> the message (q[i], sender[i] -> recipient[i]) and part[i]: 0 for a one-bit
+ * message, 0 / 1 for lo / hi of a proposal; host only.  Returns B, or BA_EINVAL
+ * (0xFFFFFFFF as uint32: a bad proto / n / m, cap < B, a missing array). */
+int ba_kenum_slots(uint32_t proto, uint32_t n, uint32_t m, uint32_t faulty_mask, uint32_t* q,
+                   uint32_t* sender, uint32_t* recipient, uint32_t* part, uint32_t cap);
+int ba_kenum_run(struct ba_ctx* ctx, const ba_params* p, uint32_t proto, uint32_t faulty_mask,
+                 uint32_t order, uint64_t batch, uint64_t* decisions, uint8_t* outcome,
+                 ba_counters* counters, uint64_t* witness);  /* counters and witness overwritten */
+/* The same walk on device buffers, enqueued on `stream` in the ctx's call order
+ * (NULL = HIP's null stream).  d_counters is accumulated into; d_witness (optional)
+ * is min-accumulated: the caller sets it to 2^64 - 1 first. */
+int ba_kenum_run_device(struct ba_ctx* ctx, const ba_params* p, uint32_t proto,
+                        uint32_t faulty_mask, uint32_t order, uint64_t batch,
+                        uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_counters,
+                        uint64_t* d_witness, void* stream);  /* accumulated, async */
+
 /* ---- one huge instance split by first-hop subtree --------
  * The subtree of first-hop lieutenant j (relay paths starting 0 -> j) needs
  * only L_0[j]; its relay levels and inner majorities are independent of the
