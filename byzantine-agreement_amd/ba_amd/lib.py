@@ -53,10 +53,13 @@ EXPORTS = ["ba_version", "ba_device_count", "ba_ctx_create", "ba_ctx_destroy", "
            "ba_king_run_trials", "ba_king_run_trials_device", "ba_king_coin_calls",
            "ba_king_phases", "ba_king3_run_trials", "ba_king3_run_trials_device",
            "ba_king3_coin_calls", "ba_king3_phases",
-           "ba_kenum_bits", "ba_kenum_slots", "ba_kenum_run", "ba_kenum_run_device"]
+           "ba_kenum_bits", "ba_kenum_slots", "ba_kenum_run", "ba_kenum_run_device",
+           "ba_smenum_bits", "ba_smenum_slots", "ba_smenum_run", "ba_smenum_run_device"]
 KENUM_KING, KENUM_KING3 = 0, 1  # the protocol of run_kenum (docs/SEMANTICS.md §11)
+SMENUM_MESSAGES, SMENUM_COALITION = 0, 1  # the form of run_smenum (docs/SEMANTICS.md §12)
+SMENUM_ANY = 0xFFFFFFFF  # smenum_slots' sender in the coalition form's relay rounds: any traitor
 KENUM_MAX_N = 16  # k_kenum is built for n = 1..16
-ENUM_MAX_BITS = 48  # BA_ENUM_MAX_BITS (docs/SEMANTICS.md §8, §11)
+ENUM_MAX_BITS = 48  # BA_ENUM_MAX_BITS (docs/SEMANTICS.md §8, §11, §12)
 NO_WITNESS = (1 << 64) - 1
 PROBE_BLOCKS = 2048  # BA_PROBE_BLOCKS
 
@@ -216,6 +219,11 @@ def load(path: str | None = None):
                                  ctypes.POINTER(Counters), ctypes.POINTER(u64)]
     lib.ba_kenum_run_device.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u32, u64, vp, vp, vp,
                                         vp, vp]
+    lib.ba_smenum_bits.argtypes = [u32, u32, u32, u32]
+    lib.ba_smenum_bits.restype = u32
+    lib.ba_smenum_slots.argtypes = [u32, u32, u32, u32, u32, vp, vp, vp, vp, u32]
+    lib.ba_smenum_run.argtypes = lib.ba_kenum_run.argtypes
+    lib.ba_smenum_run_device.argtypes = lib.ba_kenum_run_device.argtypes
     if lib.ba_version() != ABI_VERSION:
         raise RuntimeError(f"libba_hip ABI {lib.ba_version()} != {ABI_VERSION}")
     if path is None:
@@ -491,6 +499,39 @@ class Engine:
         host, so a stream that is capturing a graph takes the call."""
         _check(self.lib, self.lib.ba_kenum_run_device(
             self.handle, ctypes.byref(params), proto, faulty_mask & 0xFFFFFFFF, order, count,
+            d_decisions or None, d_outcome or None, d_counters or None, d_witness or None,
+            stream or None))
+
+    def run_smenum(self, form, n, m, faulty_mask, order, first=0, count=None, want_decisions=False,
+                   want_outcome=False, lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN,
+                   order_mode=ORDER_GIVEN, engine=ENGINE_AUTO) -> RunResult:
+        """Walk the strategies S in [first, first + count) of a traitor coalition in the
+        SM(m) case (n, m, faulty_mask, order), coded per message (SMENUM_MESSAGES) or per
+        (round, recipient, value) (SMENUM_COALITION) (docs/SEMANTICS.md §12;
+        ba_smenum_run); count=None: up to the end of the space, 2^smenum_bits.  The
+        result's `witness` is the smallest violating S of the range (decode_smstrategy
+        reads it), None when no strategy violates."""
+        if count is None:
+            b = smenum_bits(form, n, m, faulty_mask)
+            count = max(0, (1 << b) - first) if b <= ENUM_MAX_BITS else 0  # above the cap: the call says so
+        dec = np.zeros(count, np.uint64) if want_decisions else None
+        out = np.zeros(count, np.uint8) if want_outcome else None
+        p = make_params(n, m, 0, lie_mode, faulty_mode, 0, order_mode, ATTACK, engine, first)
+        cnt, wit = Counters(), ctypes.c_uint64(NO_WITNESS)
+        _check(self.lib, self.lib.ba_smenum_run(self.handle, ctypes.byref(p), form,
+                                                faulty_mask & 0xFFFFFFFF, order, count, _ptr(dec),
+                                                _ptr(out), ctypes.byref(cnt), ctypes.byref(wit)))
+        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])),
+                         witness=None if wit.value == NO_WITNESS else int(wit.value))
+
+    def run_smenum_device(self, params: Params, form: int, faulty_mask: int, order: int, count: int,
+                          d_decisions=0, d_outcome=0, d_counters=0, d_witness=0, stream=0):
+        """Enqueue strategies [params.first_trial, + count) on device pointers
+        (ba_smenum_run_device); counters accumulated, the witness (uint64, set to
+        NO_WITNESS by the caller) min-accumulated.  Fully asynchronous: nothing is copied
+        from the host, so a stream that is capturing a graph takes the call."""
+        _check(self.lib, self.lib.ba_smenum_run_device(
+            self.handle, ctypes.byref(params), form, faulty_mask & 0xFFFFFFFF, order, count,
             d_decisions or None, d_outcome or None, d_counters or None, d_witness or None,
             stream or None))
 
@@ -898,6 +939,50 @@ def encode_kstrategy(proto: int, n: int, m: int, faulty_mask: int, values) -> in
         else:
             bit = int(v)
         S |= bit << i
+    return S
+
+
+def smenum_bits(form: int, n: int, m: int, faulty_mask: int) -> int:
+    """Free bits B of an SM(m) case's coalition strategy space (ba_smenum_bits);
+    0xFFFFFFFF for a bad form / n / m."""
+    return int(load().ba_smenum_bits(form, n, m, faulty_mask & 0xFFFFFFFF))
+
+
+def smenum_slots(form: int, n: int, m: int, faulty_mask: int, order: int) -> list:
+    """[(k, sender, recipient, value)] of free bits 0..B-1 (ba_smenum_slots): the message
+    of round k that the bit sends when set; sender is SMENUM_ANY ("any traitor") in the
+    coalition form's relay rounds.  `order` decides the values only when the commander
+    is loyal."""
+    lib = load()
+    b = smenum_bits(form, n, m, faulty_mask)
+    cap = b if b != 0xFFFFFFFF else 0
+    arr = [np.zeros(max(cap, 1), np.uint32) for _ in range(4)]
+    got = lib.ba_smenum_slots(form, n, m, faulty_mask & 0xFFFFFFFF, order,
+                              *(a.ctypes.data for a in arr), cap)
+    if got < 0:
+        raise BAError(got, lib.ba_last_error().decode())
+    return [tuple(int(a[i]) for a in arr) for i in range(got)]
+
+
+def decode_smstrategy(form: int, n: int, m: int, faulty_mask: int, order: int, S: int) -> list:
+    """The sorted list of the messages (k, sender, recipient, value) that the coalition
+    sends under strategy S (docs/SEMANTICS.md §12): the free bits that are set."""
+    return sorted(s for i, s in enumerate(smenum_slots(form, n, m, faulty_mask, order)) if (S >> i) & 1)
+
+
+def encode_smstrategy(form: int, n: int, m: int, faulty_mask: int, order: int, messages) -> int:
+    """The strategy index S that sends exactly `messages`, an iterable of (k, sender,
+    recipient, value): the inverse of decode_smstrategy.  A message that is not a free
+    bit of the case raises ValueError.  `run_smenum(form, n, m, faulty_mask, order,
+    first=S & ~63, count=...)` then re-runs a hand-written strategy as element S & 63."""
+    index = {s: i for i, s in enumerate(smenum_slots(form, n, m, faulty_mask, order))}
+    S = 0
+    for msg in messages:
+        msg = tuple(int(x) for x in msg)
+        if msg not in index:
+            raise ValueError(f"message {msg} is not a free bit of (form={form}, n={n}, m={m}, "
+                             f"F={faulty_mask:#b}, order={order}): {len(index)} free bits")
+        S |= 1 << index[msg]
     return S
 
 

@@ -1726,6 +1726,161 @@ extern "C" int ba_kenum_run(ba_ctx* ctx, const ba_params* p, uint32_t proto, uin
     return rc;
 }
 
+// ---------------------------------------------------------------------------
+// SM(m) against every strategy of a traitor coalition (docs/SEMANTICS.md §12;
+// ba_smenum.hip)
+// ---------------------------------------------------------------------------
+// The numbers of a case that its bit count and slot list are made of; ok = false:
+// bad form, n or m.
+struct SmenumShape {
+    bool ok = false;
+    uint32_t F = 0, c = 0, fL = 0, ell = 0, me = 0, K = 0;
+};
+
+static SmenumShape smenum_shape(uint32_t form, uint32_t n, uint32_t m, uint32_t faulty_mask) {
+    SmenumShape s;
+    if (form > BA_SMENUM_COALITION || n < 1 || n > BA_MAX_GENERALS || m > BA_MAX_DEPTH) return s;
+    s.ok = true;
+    s.F = faulty_mask & general_mask(n);
+    s.c = s.F & 1u;
+    s.fL = (uint32_t)__builtin_popcount(s.F >> 1);
+    s.ell = n - 1 - s.fL;
+    s.me = effective_depth(n, m);
+    s.K = s.me < s.fL ? s.me : s.fL;
+    return s;
+}
+
+// B = c 2l + K s l (1 + c), s = fL senders (messages) or the coalition as one
+extern "C" uint32_t ba_smenum_bits(uint32_t form, uint32_t n, uint32_t m, uint32_t faulty_mask) {
+    const SmenumShape s = smenum_shape(form, n, m, faulty_mask);
+    if (!s.ok) return 0xFFFFFFFFu;
+    const uint64_t senders = form == BA_SMENUM_MESSAGES ? s.fL : 1;
+    const uint64_t B = (uint64_t)s.c * 2 * s.ell + (uint64_t)s.K * senders * s.ell * (1 + s.c);
+    return B > kEnumBitsSaturated ? kEnumBitsSaturated : (uint32_t)B;
+}
+
+extern "C" int ba_smenum_slots(uint32_t form, uint32_t n, uint32_t m, uint32_t faulty_mask,
+                               uint32_t order, uint32_t* k, uint32_t* sender, uint32_t* recipient,
+                               uint32_t* value, uint32_t cap) {
+    const SmenumShape s = smenum_shape(form, n, m, faulty_mask);
+    if (!s.ok) return fail(BA_EINVAL, "form=%u n=%u m=%u", form, n, m);
+    if (order > BA_OTHER) return fail(BA_EINVAL, "order=%u", order);
+    const uint32_t B = ba_smenum_bits(form, n, m, faulty_mask);
+    if (B > cap) return fail(BA_EINVAL, "cap=%u < %u free bits", cap, B);
+    if (B && (!k || !sender || !recipient || !value))
+        return fail(BA_EINVAL, "k, sender, recipient and value are required");
+    const uint32_t ob = order == BA_ATTACK ? 1 : 0;
+    uint32_t bit = 0;
+    // the free messages of round kk from sender j (general index, or "any traitor"),
+    // in recipient order: both values under a faulty commander, else the order's
+    auto round_of = [&](uint32_t kk, uint32_t j) {
+        for (uint32_t i = 1; i < n; ++i) {
+            if ((s.F >> i) & 1u) continue;
+            for (uint32_t v = 0; v < 2; ++v) {
+                if (!s.c && v != ob) continue;
+                k[bit] = kk, sender[bit] = j, recipient[bit] = i, value[bit] = v;
+                ++bit;
+            }
+        }
+    };
+    if (s.c) round_of(0, 0);
+    for (uint32_t kk = 1; kk <= s.K; ++kk) {
+        if (form == BA_SMENUM_COALITION) {
+            round_of(kk, 0xFFFFFFFFu);
+            continue;
+        }
+        for (uint32_t j = 1; j < n; ++j)
+            if ((s.F >> j) & 1u) round_of(kk, j);
+    }
+    if (bit != B) return fail(BA_EINVAL, "internal: %u free bits listed, formula %u", bit, B);
+    return (int)B;
+}
+
+static int validate_smenum(const ba_params* p, uint32_t form, uint32_t faulty_mask, uint32_t order,
+                           uint64_t batch, SmenumCase& g) {
+    if (form > BA_SMENUM_COALITION) return fail(BA_EINVAL, "form=%u", form);
+    int rc = validate_protocol(p, batch, true, true, "the SM enumeration");
+    if (rc != BA_OK) return rc;
+    if (p->faulty_mode != BA_FAULTY_GIVEN || p->order_mode != BA_ORDER_GIVEN)
+        return fail(BA_EINVAL, "faulty_mode=%u order_mode=%u: one given faulty set and order per call "
+                    "(BA_FAULTY_GIVEN, BA_ORDER_GIVEN)", p->faulty_mode, p->order_mode);
+    if (order > BA_OTHER) return fail(BA_EINVAL, "order=%u", order);
+    const uint32_t B = ba_smenum_bits(form, p->n, p->m, faulty_mask);
+    if (B > BA_ENUM_MAX_BITS)
+        return fail(BA_ETOOBIG, "form=%u n=%u m=%u faulty_mask=0x%x: %u free bits > %d", form, p->n,
+                    p->m, faulty_mask, B, BA_ENUM_MAX_BITS);
+    const uint64_t space = 1ull << B;
+    if (p->first_trial > space || batch > space - p->first_trial)
+        return fail(BA_EINVAL, "strategies [%llu, %llu + %llu) reach past 2^%u",
+                    (unsigned long long)p->first_trial, (unsigned long long)p->first_trial,
+                    (unsigned long long)batch, B);
+    const SmenumShape s = smenum_shape(form, p->n, p->m, faulty_mask);
+    g.form = form, g.n = p->n, g.m = p->m, g.me = s.me, g.fmask = s.F, g.order = order;
+    return BA_OK;
+}
+
+// Strategies [first, first + batch) of a case, kEnumLaunchMax per launch (the
+// sink's per-launch sums, at most 31 decisions per strategy, stay below 2^48).
+static int smenum_launch_range(ba_ctx* ctx, const ba_params* p, const SmenumCase& g, uint64_t first,
+                               uint64_t batch, uint64_t* d_decisions, uint8_t* d_outcome,
+                               uint64_t* d_counters, uint64_t* d_witness, void* stream) {
+    ba_params q = *p;
+    for (uint64_t t0 = 0; t0 < batch; t0 += kEnumLaunchMax) {
+        const uint64_t nt = batch - t0 < kEnumLaunchMax ? batch - t0 : kEnumLaunchMax;
+        q.first_trial = first + t0;
+        const RunArgs a = make_args(ctx, &q, nt, nullptr, nullptr, nullptr, nullptr,
+                                    d_decisions ? d_decisions + t0 : nullptr,
+                                    d_outcome ? d_outcome + t0 : nullptr, d_counters, stream);
+        HIP_TRY(launch_smenum(a, g, d_witness));
+    }
+    return BA_OK;
+}
+
+// Nothing is copied from the host: fully asynchronous, and a stream that is
+// capturing a graph takes it.
+extern "C" int ba_smenum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t form,
+                                    uint32_t faulty_mask, uint32_t order, uint64_t batch,
+                                    uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_counters,
+                                    uint64_t* d_witness, void* stream) {
+    return ordered(ctx, stream, [&] {
+        SmenumCase g{};
+        int rc = validate_smenum(p, form, faulty_mask, order, batch, g);
+        if (rc != BA_OK) return rc;
+        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
+        if (batch == 0) return BA_OK;
+        return smenum_launch_range(ctx, p, g, p->first_trial, batch, d_decisions, d_outcome, d_counters,
+                                   d_witness, stream);
+    });
+}
+
+// Host entry: host_run with no inputs to copy; counters only: one chunk, chunks of
+// kHostChunk strategies when a per-trial output is asked for (the witness
+// min-accumulates across them on the device, in the word after the counters).
+extern "C" int ba_smenum_run(ba_ctx* ctx, const ba_params* p, uint32_t form, uint32_t faulty_mask,
+                             uint32_t order, uint64_t batch, uint64_t* decisions, uint8_t* outcome,
+                             ba_counters* counters, uint64_t* witness) {
+    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
+    SmenumCase g{};
+    int rc = validate_smenum(p, form, faulty_mask, order, batch, g);
+    if (rc != BA_OK) return rc;
+    if (counters) memset(counters, 0, sizeof *counters);
+    if (witness) *witness = UINT64_MAX;
+    if (batch == 0) return BA_OK;
+    uint64_t wit = UINT64_MAX;
+    HostRun r;
+    r.decisions = decisions, r.outcome = outcome, r.counters = counters, r.tail = &wit;
+    r.chunk_env = "BA_SMENUM_HOST_CHUNK";
+    r.chunk = (decisions || outcome) ? kHostChunk : batch;
+    r.queue = [&](const ba_params& q, uint64_t nt, const uint32_t*, const uint8_t*, uint64_t* d_dec,
+                  uint8_t* d_out, void*, uint64_t* d_cnt, hipStream_t st) {
+        return ba_smenum_run_device(ctx, &q, form, faulty_mask, order, nt, d_dec, d_out, d_cnt,
+                                    d_cnt + BA_NCOUNTERS, st);
+    };
+    rc = host_run(ctx, p, batch, r);
+    if (rc == BA_OK && witness) *witness = wit;
+    return rc;
+}
+
 extern "C" int ba_split_votes_device(ba_ctx* ctx, const ba_params* p, uint64_t batch,
                                      uint32_t level, uint32_t u_begin, uint32_t u_end,
                                      const uint32_t* d_faulty, const uint8_t* d_order,

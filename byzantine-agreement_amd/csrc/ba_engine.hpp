@@ -239,4 +239,15 @@ struct KenumCase {
 };
 hipError_t launch_kenum(const RunArgs& a, const KenumCase& g, uint64_t* witness);
 
+// SM(m) against every strategy of a traitor coalition (ba_smenum.hip,
+// docs/SEMANTICS.md §12): trial t is strategy S = t.  Everything the kernel needs is
+// in the case: no map, no upload.  k_smenum keeps two planes per loyal lieutenant in
+// registers and is instantiated per form and padded loyal count, for every n <= 32.
+struct SmenumCase {
+    uint32_t form;  // BA_SMENUM_MESSAGES / BA_SMENUM_COALITION
+    uint32_t n, m, me;
+    uint32_t fmask, order;  // fmask masked to n bits; order code 0..2
+};
+hipError_t launch_smenum(const RunArgs& a, const SmenumCase& g, uint64_t* witness);
+
 }  // namespace ba

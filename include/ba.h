@@ -509,6 +509,65 @@ int ba_kenum_run_device(struct ba_ctx* ctx, const ba_params* p, uint32_t proto,
                         uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_counters,
                         uint64_t* d_witness, void* stream);  /* accumulated, async */
 
+/* ---- SM(m) against every strategy of a traitor coalition ------------------------
+ * ba_sm_run_trials' traitors flip coins, relay only what they accepted a round ago
+ * and share nothing; Lamport's theorem (agreement for any f <= m, any n) speaks of
+ * traitors that pool their signatures and pick their messages.  These entries walk
+ * every such strategy of one case (form, n, m, faulty set, order) (docs/SEMANTICS.md
+ * §12; no ba.py analogue).  With me = min(m, n-2), c = [0 in F], l loyal and fL
+ * faulty lieutenants and K = min(me, fL): in round k = 1..K any faulty lieutenant can
+ * deliver a validly signed value to a loyal one whatever went before -- either value
+ * when the commander is faulty, the order's value alone when it is loyal.  Later
+ * rounds would need a loyal signature, which exists only on values every loyal
+ * lieutenant was shown already: such messages change nothing and are not coded.
+ * A free bit is one such message, 1 = sent:
+ *   BA_SMENUM_MESSAGES   bits in (k, sender, recipient, v) ascending order, retreat
+ *                        before attack; round 0 (the faulty commander's) first:
+ *                          B = c 2l + K fL l (1 + c)
+ *   BA_SMENUM_COALITION  a recipient accepts from any sender, so one bit per
+ *                        (k, recipient, v): "some traitor delivers v in round k":
+ *                          B = c 2l + K l (1 + c)
+ *                        A message-form strategy and its projection (OR over the
+ *                        senders) decide alike.  Rates are over the coded space of
+ *                        the form used.
+ * Loyal generals follow SM(m); faulty lieutenants keep V honestly on what loyal
+ * senders show them (one V for all of them) and decide choice(V).
+ * Trial t of a call is strategy S = t: a call covers S in [p->first_trial,
+ * p->first_trial + batch), first_trial a multiple of 64, ending at or below 2^B
+ * (else BA_EINVAL).  p supplies n, m and first_trial; seed and f are unused.
+ * p->lie_mode must be BA_LIE_PHILOX (TABLE: BA_ENOTSUP), p->engine BA_ENGINE_AUTO,
+ * p->faulty_mode BA_FAULTY_GIVEN and p->order_mode BA_ORDER_GIVEN (else BA_EINVAL);
+ * form > 1, order > BA_OTHER, m > 8 and n outside 1..32 are BA_EINVAL.
+ * B > BA_ENUM_MAX_BITS is BA_ETOOBIG; every n <= 32 is accepted.
+ * decisions / outcome / counters: the layouts above, in-bound is |F| <= m.  witness:
+ * the smallest S of the range that violates IC1 or (IC2 applicable) IC2, in bound or
+ * not, or 2^64 - 1 when none does.  batch = 0: BA_OK, zero counters, witness
+ * 2^64 - 1.  At most 2^40 strategies go into one launch.  Nothing is copied from
+ * host memory: ba_smenum_run_device is fully asynchronous and may be captured in a
+ * graph. */
+#define BA_SMENUM_MESSAGES 0
+#define BA_SMENUM_COALITION 1
+/* B; host only.  0xFFFFFFFF for form > 1, n outside 1..32 or m > 8; saturates at
+ * 0xFFFFFFFE. */
+uint32_t ba_smenum_bits(uint32_t form, uint32_t n, uint32_t m, uint32_t faulty_mask);
+/* bit i -> the message (round k[i], sender[i] -> recipient[i], value[i]); sender is
+ * 0xFFFFFFFF ("any traitor") in the coalition form's relay rounds.  order decides
+ * value[] only when the commander is loyal.  Host only.  Returns B, or BA_EINVAL (a
+ * bad form / n / m / order, cap < B, a missing array). */
+int ba_smenum_slots(uint32_t form, uint32_t n, uint32_t m, uint32_t faulty_mask, uint32_t order,
+                    uint32_t* k, uint32_t* sender, uint32_t* recipient, uint32_t* value,
+                    uint32_t cap);
+int ba_smenum_run(struct ba_ctx* ctx, const ba_params* p, uint32_t form, uint32_t faulty_mask,
+                  uint32_t order, uint64_t batch, uint64_t* decisions, uint8_t* outcome,
+                  ba_counters* counters, uint64_t* witness);  /* counters and witness overwritten */
+/* The same walk on device buffers, enqueued on `stream` in the ctx's call order
+ * (NULL = HIP's null stream).  d_counters is accumulated into; d_witness (optional)
+ * is min-accumulated: the caller sets it to 2^64 - 1 first. */
+int ba_smenum_run_device(struct ba_ctx* ctx, const ba_params* p, uint32_t form,
+                         uint32_t faulty_mask, uint32_t order, uint64_t batch,
+                         uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_counters,
+                         uint64_t* d_witness, void* stream);  /* accumulated, async */
+
 /* ---- one huge instance split by first-hop subtree --------
  * The subtree of first-hop lieutenant j (relay paths starting 0 -> j) needs
  * only L_0[j]; its relay levels and inner majorities are independent of the
