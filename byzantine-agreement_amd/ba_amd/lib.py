@@ -437,6 +437,29 @@ class Engine:
             d_decisions or None, d_outcome or None, d_settled or None, d_counters or None,
             stream or None))
 
+    def _run_enum(self, fn, bits, lead, n, m, faulty_mask, order, first, count, want_decisions, want_outcome,
+                  lie_mode, faulty_mode, order_mode, engine) -> RunResult:
+        """The host entry `fn` of one enumeration over strategies [first, first + count).
+        bits: the case's free bits, for count=None; lead: the entry's arguments between
+        params and faulty_mask (proto / form), () when it has none."""
+        if count is None:
+            count = max(0, (1 << bits) - first) if bits <= ENUM_MAX_BITS else 0  # above the cap: the call says so
+        dec = np.zeros(count, np.uint64) if want_decisions else None
+        out = np.zeros(count, np.uint8) if want_outcome else None
+        p = make_params(n, m, 0, lie_mode, faulty_mode, 0, order_mode, ATTACK, engine, first)
+        cnt, wit = Counters(), ctypes.c_uint64(NO_WITNESS)
+        _check(self.lib, fn(self.handle, ctypes.byref(p), *lead, faulty_mask & 0xFFFFFFFF, order, count,
+                            _ptr(dec), _ptr(out), ctypes.byref(cnt), ctypes.byref(wit)))
+        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])),
+                         witness=None if wit.value == NO_WITNESS else int(wit.value))
+
+    def _run_enum_device(self, fn, lead, params, faulty_mask, order, count, d_decisions, d_outcome,
+                         d_counters, d_witness, stream):
+        """The device entry `fn` of one enumeration; lead as in _run_enum."""
+        _check(self.lib, fn(self.handle, ctypes.byref(params), *lead, faulty_mask & 0xFFFFFFFF, order, count,
+                            d_decisions or None, d_outcome or None, d_counters or None, d_witness or None,
+                            stream or None))
+
     def run_enum(self, n, m, faulty_mask, order, first=0, count=None, want_decisions=False,
                  want_outcome=False, lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN,
                  order_mode=ORDER_GIVEN, engine=ENGINE_AUTO) -> RunResult:
@@ -444,18 +467,9 @@ class Engine:
         faulty_mask, order) (docs/SEMANTICS.md §8; ba_enum_run); count=None: up to the end
         of the space, 2^enum_bits.  The result's `witness` is the smallest violating S of
         the range (decode_strategy reads it), None when no strategy violates."""
-        if count is None:
-            b = enum_bits(n, m, faulty_mask)
-            count = max(0, (1 << b) - first) if b <= ENUM_MAX_BITS else 0  # above the cap: the call says so
-        dec = np.zeros(count, np.uint64) if want_decisions else None
-        out = np.zeros(count, np.uint8) if want_outcome else None
-        p = make_params(n, m, 0, lie_mode, faulty_mode, 0, order_mode, ATTACK, engine, first)
-        cnt, wit = Counters(), ctypes.c_uint64(NO_WITNESS)
-        _check(self.lib, self.lib.ba_enum_run(self.handle, ctypes.byref(p), faulty_mask & 0xFFFFFFFF,
-                                              order, count, _ptr(dec), _ptr(out), ctypes.byref(cnt),
-                                              ctypes.byref(wit)))
-        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])),
-                         witness=None if wit.value == NO_WITNESS else int(wit.value))
+        return self._run_enum(self.lib.ba_enum_run, enum_bits(n, m, faulty_mask), (), n, m,
+                              faulty_mask, order, first, count, want_decisions, want_outcome, lie_mode,
+                              faulty_mode, order_mode, engine)
 
     def run_enum_device(self, params: Params, faulty_mask: int, order: int, count: int,
                         d_decisions=0, d_outcome=0, d_counters=0, d_witness=0, stream=0):
@@ -465,10 +479,8 @@ class Engine:
         first copies the case's slot map from host memory and returns only after the
         stream's earlier work has drained (include/ba.h).  On a stream that is capturing a
         graph it raises BAError(ENOTSUP) and queues nothing."""
-        _check(self.lib, self.lib.ba_enum_run_device(
-            self.handle, ctypes.byref(params), faulty_mask & 0xFFFFFFFF, order, count,
-            d_decisions or None, d_outcome or None, d_counters or None, d_witness or None,
-            stream or None))
+        self._run_enum_device(self.lib.ba_enum_run_device, (), params, faulty_mask, order, count,
+                              d_decisions, d_outcome, d_counters, d_witness, stream)
 
     def run_kenum(self, proto, n, m, faulty_mask, order, first=0, count=None, want_decisions=False,
                   want_outcome=False, lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN,
@@ -478,18 +490,9 @@ class Engine:
         (docs/SEMANTICS.md §11; ba_kenum_run); count=None: up to the end of the space,
         2^kenum_bits.  The result's `witness` is the smallest violating S of the range
         (decode_kstrategy reads it), None when no strategy violates."""
-        if count is None:
-            b = kenum_bits(proto, n, m, faulty_mask)
-            count = max(0, (1 << b) - first) if b <= ENUM_MAX_BITS else 0  # above the cap: the call says so
-        dec = np.zeros(count, np.uint64) if want_decisions else None
-        out = np.zeros(count, np.uint8) if want_outcome else None
-        p = make_params(n, m, 0, lie_mode, faulty_mode, 0, order_mode, ATTACK, engine, first)
-        cnt, wit = Counters(), ctypes.c_uint64(NO_WITNESS)
-        _check(self.lib, self.lib.ba_kenum_run(self.handle, ctypes.byref(p), proto,
-                                               faulty_mask & 0xFFFFFFFF, order, count, _ptr(dec),
-                                               _ptr(out), ctypes.byref(cnt), ctypes.byref(wit)))
-        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])),
-                         witness=None if wit.value == NO_WITNESS else int(wit.value))
+        return self._run_enum(self.lib.ba_kenum_run, kenum_bits(proto, n, m, faulty_mask), (proto,), n, m,
+                              faulty_mask, order, first, count, want_decisions, want_outcome, lie_mode,
+                              faulty_mode, order_mode, engine)
 
     def run_kenum_device(self, params: Params, proto: int, faulty_mask: int, order: int, count: int,
                          d_decisions=0, d_outcome=0, d_counters=0, d_witness=0, stream=0):
@@ -497,10 +500,8 @@ class Engine:
         (ba_kenum_run_device); counters accumulated, the witness (uint64, set to NO_WITNESS
         by the caller) min-accumulated.  Fully asynchronous: nothing is copied from the
         host, so a stream that is capturing a graph takes the call."""
-        _check(self.lib, self.lib.ba_kenum_run_device(
-            self.handle, ctypes.byref(params), proto, faulty_mask & 0xFFFFFFFF, order, count,
-            d_decisions or None, d_outcome or None, d_counters or None, d_witness or None,
-            stream or None))
+        self._run_enum_device(self.lib.ba_kenum_run_device, (proto,), params, faulty_mask, order, count,
+                              d_decisions, d_outcome, d_counters, d_witness, stream)
 
     def run_smenum(self, form, n, m, faulty_mask, order, first=0, count=None, want_decisions=False,
                    want_outcome=False, lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN,
@@ -511,18 +512,9 @@ class Engine:
         ba_smenum_run); count=None: up to the end of the space, 2^smenum_bits.  The
         result's `witness` is the smallest violating S of the range (decode_smstrategy
         reads it), None when no strategy violates."""
-        if count is None:
-            b = smenum_bits(form, n, m, faulty_mask)
-            count = max(0, (1 << b) - first) if b <= ENUM_MAX_BITS else 0  # above the cap: the call says so
-        dec = np.zeros(count, np.uint64) if want_decisions else None
-        out = np.zeros(count, np.uint8) if want_outcome else None
-        p = make_params(n, m, 0, lie_mode, faulty_mode, 0, order_mode, ATTACK, engine, first)
-        cnt, wit = Counters(), ctypes.c_uint64(NO_WITNESS)
-        _check(self.lib, self.lib.ba_smenum_run(self.handle, ctypes.byref(p), form,
-                                                faulty_mask & 0xFFFFFFFF, order, count, _ptr(dec),
-                                                _ptr(out), ctypes.byref(cnt), ctypes.byref(wit)))
-        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])),
-                         witness=None if wit.value == NO_WITNESS else int(wit.value))
+        return self._run_enum(self.lib.ba_smenum_run, smenum_bits(form, n, m, faulty_mask), (form,), n, m,
+                              faulty_mask, order, first, count, want_decisions, want_outcome, lie_mode,
+                              faulty_mode, order_mode, engine)
 
     def run_smenum_device(self, params: Params, form: int, faulty_mask: int, order: int, count: int,
                           d_decisions=0, d_outcome=0, d_counters=0, d_witness=0, stream=0):
@@ -530,10 +522,8 @@ class Engine:
         (ba_smenum_run_device); counters accumulated, the witness (uint64, set to
         NO_WITNESS by the caller) min-accumulated.  Fully asynchronous: nothing is copied
         from the host, so a stream that is capturing a graph takes the call."""
-        _check(self.lib, self.lib.ba_smenum_run_device(
-            self.handle, ctypes.byref(params), form, faulty_mask & 0xFFFFFFFF, order, count,
-            d_decisions or None, d_outcome or None, d_counters or None, d_witness or None,
-            stream or None))
+        self._run_enum_device(self.lib.ba_smenum_run_device, (form,), params, faulty_mask, order, count,
+                              d_decisions, d_outcome, d_counters, d_witness, stream)
 
     def stream(self) -> int:
         """The ctx's own HIP stream (ba_ctx_stream), as an int handle."""

@@ -1039,10 +1039,11 @@ extern "C" int ba_run_trials_device(ba_ctx* ctx, const ba_params* p, uint64_t ba
 }
 
 // ---------------------------------------------------------------------------
-// The wave protocols beside OM(m): SM, ADV, KING, KING3, ENUM.  A protocol is its
-// validation tail (validate_protocol plus what only it checks), a device entry
-// (protocol_device_entry with its launch) and a host entry (host_run with a
-// HostRun that says what it stages and how a chunk is queued).
+// The wave protocols beside OM(m): SM, ADV, KING, KING3 and the enumerations.  A
+// protocol is its validation tail (validate_protocol plus what only it checks), a
+// device entry (protocol_device_entry with its launch; the enumerations':
+// enum_device_entry) and a host entry (host_run with a HostRun that says what it
+// stages and how a chunk is queued).
 // ---------------------------------------------------------------------------
 // The checks every protocol shares, in the order that decides which error wins;
 // `what` names the protocol in the two messages of its own.
@@ -1105,8 +1106,8 @@ struct HostRun {
     bool extra_behind_dec = false;
     const char* chunk_env = nullptr;   // tests: chunk a small batch (a multiple of 64)
     uint64_t chunk = kHostChunk;       // without the override
-    uint64_t* tail = nullptr;          // enum: the word after the counters, preset to all-ones
-    std::function<int(hipStream_t)> before;  // enum: once, ahead of the first chunk
+    uint64_t* tail = nullptr;          // the enumerations: the word after the counters, preset to all-ones
+    std::function<int(hipStream_t)> before;  // the enumerations: once, ahead of the first chunk
     HostQueue queue;
 };
 
@@ -1371,9 +1372,121 @@ extern "C" int ba_king3_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t pol
 }
 
 // ---------------------------------------------------------------------------
-// OM(m) against every traitor strategy of one case (docs/SEMANTICS.md §8; ba_enum.hip)
+// The exhaustive enumerations ENUM, KENUM and SMENUM (docs/SEMANTICS.md §8, §11,
+// §12): trial t of a call is strategy t of one case.  What they share: the
+// validation tail, the launch range, the device entry and the host entry.  An
+// enumeration is its bit count and slot list, its case set-up and its launch_*.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kEnumBitsSaturated = 0xFFFFFFFEu;
+
+// One launch takes at most 2^40 strategies: the counter sink's per-launch sums
+// (at most 31 decisions per strategy) stay below 2^48.
+constexpr uint64_t kEnumLaunchMax = 1ull << 40;
+
+// The checks of an enumeration after its own leading argument, in the order that
+// decides which error wins: validate_protocol, one given faulty set and order,
+// pre() (what the protocol checks ahead of the bit cap), the cap on the case's B free
+// bits, the range inside 2^B.  `prefix` names the case ahead of n in the cap's message.
+template <typename Pre>
+static int validate_enumeration(const ba_params* p, uint64_t batch, const char* what, uint32_t max_m,
+                                uint32_t faulty_mask, uint32_t order, uint32_t B, const char* prefix,
+                                Pre&& pre) {
+    int rc = validate_protocol(p, batch, true, true, what, max_m);
+    if (rc != BA_OK) return rc;
+    if (p->faulty_mode != BA_FAULTY_GIVEN || p->order_mode != BA_ORDER_GIVEN)
+        return fail(BA_EINVAL, "faulty_mode=%u order_mode=%u: one given faulty set and order per call "
+                    "(BA_FAULTY_GIVEN, BA_ORDER_GIVEN)", p->faulty_mode, p->order_mode);
+    if (order > BA_OTHER) return fail(BA_EINVAL, "order=%u", order);
+    if ((rc = pre()) != BA_OK) return rc;
+    if (B > BA_ENUM_MAX_BITS)
+        return fail(BA_ETOOBIG, "%sn=%u m=%u faulty_mask=0x%x: %u free bits > %d", prefix, p->n, p->m,
+                    faulty_mask, B, BA_ENUM_MAX_BITS);
+    const uint64_t space = 1ull << B;  // B <= 48
+    if (p->first_trial > space || batch > space - p->first_trial)
+        return fail(BA_EINVAL, "strategies [%llu, %llu + %llu) reach past 2^%u",
+                    (unsigned long long)p->first_trial, (unsigned long long)p->first_trial,
+                    (unsigned long long)batch, B);
+    return BA_OK;
+}
+
+// Strategies [first, first + batch) of a case, kEnumLaunchMax per launch(args, witness).
+template <typename Launch>
+static int enum_launch_range(ba_ctx* ctx, const ba_params* p, uint64_t first, uint64_t batch,
+                             uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_counters,
+                             uint64_t* d_witness, void* stream, Launch&& launch) {
+    ba_params q = *p;
+    for (uint64_t t0 = 0; t0 < batch; t0 += kEnumLaunchMax) {
+        const uint64_t nt = batch - t0 < kEnumLaunchMax ? batch - t0 : kEnumLaunchMax;
+        q.first_trial = first + t0;
+        const RunArgs a = make_args(ctx, &q, nt, nullptr, nullptr, nullptr, nullptr,
+                                    d_decisions ? d_decisions + t0 : nullptr,
+                                    d_outcome ? d_outcome + t0 : nullptr, d_counters, stream);
+        HIP_TRY(launch(a, d_witness));
+    }
+    return BA_OK;
+}
+
+// The body of an enumeration's device entry: ordered on the ctx, check() first, then
+// prepare(stream) (what the kernels read that is not an argument) and the launches.
+// no_capture: why a stream that is capturing a graph is refused, before anything is
+// queued on it; NULL: nothing is copied from the host, the call is fully asynchronous
+// and a capturing stream takes it.
+template <typename Check, typename Prepare, typename Launch>
+static int enum_device_entry(ba_ctx* ctx, const ba_params* p, uint64_t batch, uint64_t* d_decisions,
+                             uint8_t* d_outcome, uint64_t* d_counters, uint64_t* d_witness,
+                             void* stream, const char* no_capture, Check&& check, Prepare&& prepare,
+                             Launch&& launch) {
+    if (no_capture && ctx && stream_capturing((hipStream_t)stream)) return fail(BA_ENOTSUP, "%s", no_capture);
+    return ordered(ctx, stream, [&] {
+        int rc = check();
+        if (rc != BA_OK) return rc;
+        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
+        if (batch == 0) return BA_OK;
+        if ((rc = prepare((hipStream_t)stream)) != BA_OK) return rc;
+        return enum_launch_range(ctx, p, p->first_trial, batch, d_decisions, d_outcome, d_counters,
+                                 d_witness, stream, launch);
+    });
+}
+
+// An enumeration's host entry: host_run with no inputs to copy; counters only: one
+// chunk, chunks of kHostChunk strategies when a per-trial output is asked for (the
+// witness min-accumulates across them on the device, in the word after the
+// counters).  The case is validated and prepared once for all the chunks.
+template <typename Check, typename Prepare, typename Launch>
+static int enum_host_entry(ba_ctx* ctx, const ba_params* p, uint64_t batch, uint64_t* decisions,
+                           uint8_t* outcome, ba_counters* counters, uint64_t* witness,
+                           const char* chunk_env, Check&& check, Prepare&& prepare, Launch&& launch) {
+    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
+    int rc = check();
+    if (rc != BA_OK) return rc;
+    if (counters) memset(counters, 0, sizeof *counters);
+    if (witness) *witness = UINT64_MAX;
+    if (batch == 0) return BA_OK;
+    uint64_t wit = UINT64_MAX;
+    HostRun r;
+    r.decisions = decisions, r.outcome = outcome, r.counters = counters, r.tail = &wit;
+    r.chunk_env = chunk_env;
+    r.chunk = (decisions || outcome) ? kHostChunk : batch;
+    r.before = [&](hipStream_t st) {
+        const int rc = prepare(st);
+        (void)ctx_mark(ctx, st);  // whatever follows: work of this ctx is queued on st
+        return rc;
+    };
+    r.queue = [&](const ba_params& q, uint64_t nt, const uint32_t*, const uint8_t*, uint64_t* d_dec,
+                  uint8_t* d_out, void*, uint64_t* d_cnt, hipStream_t st) {
+        return enum_launch_range(ctx, p, q.first_trial, nt, d_dec, d_out, d_cnt, d_cnt + BA_NCOUNTERS, st,
+                                 launch);
+    };
+    rc = host_run(ctx, p, batch, r);
+    if (rc == BA_OK && witness) *witness = wit;
+    return rc;
+}
+
+static int enum_no_prepare(hipStream_t) { return BA_OK; }
+
+// ---------------------------------------------------------------------------
+// OM(m) against every traitor strategy of one case (docs/SEMANTICS.md §8; ba_enum.hip)
+// ---------------------------------------------------------------------------
 
 // B = [F_0](L - f_L) + f_L (L - f_L) sum_{k=1..me} P(L-2, k-1)
 extern "C" uint32_t ba_enum_bits(uint32_t n, uint32_t m, uint32_t faulty_mask) {
@@ -1467,26 +1580,14 @@ extern "C" int ba_enum_slots(uint32_t n, uint32_t m, uint32_t faulty_mask, uint3
     return (int)B;
 }
 
-// One launch takes at most 2^40 strategies: the counter sink's per-launch sums
-// (at most 31 decisions per strategy) stay below 2^48.
-constexpr uint64_t kEnumLaunchMax = 1ull << 40;
-
+// enum_plan's own checks (the slot map must fit LDS) come ahead of the bit cap.
 static int validate_enum(const ba_params* p, uint32_t faulty_mask, uint32_t order, uint64_t batch,
                          EnumPlan& pl) {
-    int rc = validate_protocol(p, batch, true, true, "the enumeration");
-    if (rc != BA_OK) return rc;
-    if (p->faulty_mode != BA_FAULTY_GIVEN || p->order_mode != BA_ORDER_GIVEN)
-        return fail(BA_EINVAL, "faulty_mode=%u order_mode=%u: one given faulty set and order per call "
-                    "(BA_FAULTY_GIVEN, BA_ORDER_GIVEN)", p->faulty_mode, p->order_mode);
-    if (order > BA_OTHER) return fail(BA_EINVAL, "order=%u", order);
-    if ((rc = enum_plan(p->n, p->m, faulty_mask, pl)) != BA_OK) return rc;
+    const uint32_t B = p ? ba_enum_bits(p->n, p->m, faulty_mask) : 0;
+    int rc = validate_enumeration(p, batch, "the enumeration", BA_MAX_DEPTH, faulty_mask, order, B, "",
+                                  [&] { return enum_plan(p->n, p->m, faulty_mask, pl); });
     pl.g.order = order;
-    const uint64_t space = 1ull << pl.level.size();  // B <= 48
-    if (p->first_trial > space || batch > space - p->first_trial)
-        return fail(BA_EINVAL, "strategies [%llu, %llu + %llu) reach past 2^%u",
-                    (unsigned long long)p->first_trial, (unsigned long long)p->first_trial,
-                    (unsigned long long)batch, (unsigned)pl.level.size());
-    return BA_OK;
+    return rc;
 }
 
 // The case's slot map into the ctx's scratch, on `stream` (in the ctx's call order: the
@@ -1504,75 +1605,32 @@ static int enum_upload(ba_ctx* ctx, const EnumPlan& pl, hipStream_t stream) {
     return BA_OK;
 }
 
-// Strategies [first, first + batch) of an uploaded case, kEnumLaunchMax per launch.
-static int enum_launch_range(ba_ctx* ctx, const ba_params* p, const EnumPlan& pl, uint64_t first,
-                             uint64_t batch, uint64_t* d_decisions, uint8_t* d_outcome,
-                             uint64_t* d_counters, uint64_t* d_witness, void* stream) {
-    ba_params q = *p;
-    for (uint64_t t0 = 0; t0 < batch; t0 += kEnumLaunchMax) {
-        const uint64_t nt = batch - t0 < kEnumLaunchMax ? batch - t0 : kEnumLaunchMax;
-        q.first_trial = first + t0;
-        const RunArgs a = make_args(ctx, &q, nt, nullptr, nullptr, nullptr, nullptr,
-                                    d_decisions ? d_decisions + t0 : nullptr,
-                                    d_outcome ? d_outcome + t0 : nullptr, d_counters, stream);
-        HIP_TRY(launch_enum(a, pl.g, (const uint8_t*)ctx->scratch.p, d_witness));
-    }
-    return BA_OK;
-}
-
+// The map upload is why the device entry waits on the host and refuses a capture: the
+// copy would become a graph node whose source, the plan's host vector, is gone when a
+// replay reads it.
 extern "C" int ba_enum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t faulty_mask,
                                   uint32_t order, uint64_t batch, uint64_t* d_decisions,
                                   uint8_t* d_outcome, uint64_t* d_counters, uint64_t* d_witness,
                                   void* stream) {
-    // refused before anything is queued on the stream: the map copy (enum_upload)
-    // would become a graph node whose source, the plan's host vector, is gone
-    // when a replay reads it
-    if (ctx && stream_capturing((hipStream_t)stream))
-        return fail(BA_ENOTSUP, "ba_enum_run_device on a stream that is capturing a graph: its slot "
-                    "map is copied from host memory that does not outlive the call");
-    return ordered(ctx, stream, [&] {
-        EnumPlan pl;
-        int rc = validate_enum(p, faulty_mask, order, batch, pl);
-        if (rc != BA_OK) return rc;
-        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
-        if (batch == 0) return BA_OK;
-        if ((rc = enum_upload(ctx, pl, (hipStream_t)stream)) != BA_OK) return rc;
-        return enum_launch_range(ctx, p, pl, p->first_trial, batch, d_decisions, d_outcome,
-                                 d_counters, d_witness, stream);
-    });
+    EnumPlan pl;
+    return enum_device_entry(
+        ctx, p, batch, d_decisions, d_outcome, d_counters, d_witness, stream,
+        "ba_enum_run_device on a stream that is capturing a graph: its slot map is copied from host "
+        "memory that does not outlive the call",
+        [&] { return validate_enum(p, faulty_mask, order, batch, pl); },
+        [&](hipStream_t st) { return enum_upload(ctx, pl, st); },
+        [&](const RunArgs& a, uint64_t* w) { return launch_enum(a, pl.g, (const uint8_t*)ctx->scratch.p, w); });
 }
 
-// Host entry: host_run with no inputs to copy; counters only: one chunk, chunks of
-// kHostChunk strategies when a per-trial output is asked for (the witness
-// min-accumulates across them on the device, in the word after the counters).
-// The case is planned and its slot map uploaded once for all the chunks.
 extern "C" int ba_enum_run(ba_ctx* ctx, const ba_params* p, uint32_t faulty_mask, uint32_t order,
                            uint64_t batch, uint64_t* decisions, uint8_t* outcome,
                            ba_counters* counters, uint64_t* witness) {
-    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
     EnumPlan pl;
-    int rc = validate_enum(p, faulty_mask, order, batch, pl);
-    if (rc != BA_OK) return rc;
-    if (counters) memset(counters, 0, sizeof *counters);
-    if (witness) *witness = UINT64_MAX;
-    if (batch == 0) return BA_OK;
-    uint64_t wit = UINT64_MAX;
-    HostRun r;
-    r.decisions = decisions, r.outcome = outcome, r.counters = counters, r.tail = &wit;
-    r.chunk_env = "BA_ENUM_HOST_CHUNK";
-    r.chunk = (decisions || outcome) ? kHostChunk : batch;
-    r.before = [&](hipStream_t st) {
-        const int up = enum_upload(ctx, pl, st);
-        (void)ctx_mark(ctx, st);  // whatever follows: work of this ctx is queued on st
-        return up;
-    };
-    r.queue = [&](const ba_params& q, uint64_t nt, const uint32_t*, const uint8_t*, uint64_t* d_dec,
-                  uint8_t* d_out, void*, uint64_t* d_cnt, hipStream_t st) {
-        return enum_launch_range(ctx, p, pl, q.first_trial, nt, d_dec, d_out, d_cnt, d_cnt + BA_NCOUNTERS, st);
-    };
-    rc = host_run(ctx, p, batch, r);
-    if (rc == BA_OK && witness) *witness = wit;
-    return rc;
+    return enum_host_entry(
+        ctx, p, batch, decisions, outcome, counters, witness, "BA_ENUM_HOST_CHUNK",
+        [&] { return validate_enum(p, faulty_mask, order, batch, pl); },
+        [&](hipStream_t st) { return enum_upload(ctx, pl, st); },
+        [&](const RunArgs& a, uint64_t* w) { return launch_enum(a, pl.g, (const uint8_t*)ctx->scratch.p, w); });
 }
 
 // ---------------------------------------------------------------------------
@@ -1640,90 +1698,42 @@ extern "C" int ba_kenum_slots(uint32_t proto, uint32_t n, uint32_t m, uint32_t f
 static int validate_kenum(const ba_params* p, uint32_t proto, uint32_t faulty_mask, uint32_t order,
                           uint64_t batch, KenumCase& g) {
     if (proto > BA_KENUM_KING3) return fail(BA_EINVAL, "proto=%u", proto);
-    int rc = validate_protocol(p, batch, true, true, "the King enumeration",
-                               proto == BA_KENUM_KING ? (uint32_t)BA_MAX_DEPTH : kKing3MaxM);
+    char prefix[24];
+    snprintf(prefix, sizeof prefix, "proto=%u ", proto);
+    const uint32_t B = p ? ba_kenum_bits(proto, p->n, p->m, faulty_mask) : 0;
+    int rc = validate_enumeration(
+        p, batch, "the King enumeration", proto == BA_KENUM_KING ? (uint32_t)BA_MAX_DEPTH : kKing3MaxM,
+        faulty_mask, order, B, prefix, [&] {
+            if (p->n > kKenumMaxN)
+                return fail(BA_ETOOBIG, "n=%u > %u: k_kenum keeps one plane per general in registers", p->n,
+                            kKenumMaxN);
+            return (int)BA_OK;
+        });
     if (rc != BA_OK) return rc;
-    if (p->faulty_mode != BA_FAULTY_GIVEN || p->order_mode != BA_ORDER_GIVEN)
-        return fail(BA_EINVAL, "faulty_mode=%u order_mode=%u: one given faulty set and order per call "
-                    "(BA_FAULTY_GIVEN, BA_ORDER_GIVEN)", p->faulty_mode, p->order_mode);
-    if (order > BA_OTHER) return fail(BA_EINVAL, "order=%u", order);
-    if (p->n > kKenumMaxN)
-        return fail(BA_ETOOBIG, "n=%u > %u: k_kenum keeps one plane per general in registers", p->n,
-                    kKenumMaxN);
-    const uint32_t B = ba_kenum_bits(proto, p->n, p->m, faulty_mask);
-    if (B > BA_ENUM_MAX_BITS)
-        return fail(BA_ETOOBIG, "proto=%u n=%u m=%u faulty_mask=0x%x: %u free bits > %d", proto, p->n,
-                    p->m, faulty_mask, B, BA_ENUM_MAX_BITS);
-    const uint64_t space = 1ull << B;
-    if (p->first_trial > space || batch > space - p->first_trial)
-        return fail(BA_EINVAL, "strategies [%llu, %llu + %llu) reach past 2^%u",
-                    (unsigned long long)p->first_trial, (unsigned long long)p->first_trial,
-                    (unsigned long long)batch, B);
     const KenumShape s = kenum_shape(proto, p->n, p->m, faulty_mask);
     g.proto = proto, g.m = p->m, g.phases = s.P, g.fmask = s.F, g.order = order;
     return BA_OK;
 }
 
-// Strategies [first, first + batch) of a case, kEnumLaunchMax per launch (the
-// sink's per-launch sums, at most 15 decisions per strategy, stay below 2^48).
-static int kenum_launch_range(ba_ctx* ctx, const ba_params* p, const KenumCase& g, uint64_t first,
-                              uint64_t batch, uint64_t* d_decisions, uint8_t* d_outcome,
-                              uint64_t* d_counters, uint64_t* d_witness, void* stream) {
-    ba_params q = *p;
-    for (uint64_t t0 = 0; t0 < batch; t0 += kEnumLaunchMax) {
-        const uint64_t nt = batch - t0 < kEnumLaunchMax ? batch - t0 : kEnumLaunchMax;
-        q.first_trial = first + t0;
-        const RunArgs a = make_args(ctx, &q, nt, nullptr, nullptr, nullptr, nullptr,
-                                    d_decisions ? d_decisions + t0 : nullptr,
-                                    d_outcome ? d_outcome + t0 : nullptr, d_counters, stream);
-        HIP_TRY(launch_kenum(a, g, d_witness));
-    }
-    return BA_OK;
-}
-
-// Nothing is copied from the host: fully asynchronous, and a stream that is
-// capturing a graph takes it.
 extern "C" int ba_kenum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t proto,
                                    uint32_t faulty_mask, uint32_t order, uint64_t batch,
                                    uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_counters,
                                    uint64_t* d_witness, void* stream) {
-    return ordered(ctx, stream, [&] {
-        KenumCase g{};
-        int rc = validate_kenum(p, proto, faulty_mask, order, batch, g);
-        if (rc != BA_OK) return rc;
-        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
-        if (batch == 0) return BA_OK;
-        return kenum_launch_range(ctx, p, g, p->first_trial, batch, d_decisions, d_outcome, d_counters,
-                                  d_witness, stream);
-    });
+    KenumCase g{};
+    return enum_device_entry(
+        ctx, p, batch, d_decisions, d_outcome, d_counters, d_witness, stream, nullptr,
+        [&] { return validate_kenum(p, proto, faulty_mask, order, batch, g); }, enum_no_prepare,
+        [&](const RunArgs& a, uint64_t* w) { return launch_kenum(a, g, w); });
 }
 
-// Host entry: host_run with no inputs to copy; counters only: one chunk, chunks of
-// kHostChunk strategies when a per-trial output is asked for (the witness
-// min-accumulates across them on the device, in the word after the counters).
 extern "C" int ba_kenum_run(ba_ctx* ctx, const ba_params* p, uint32_t proto, uint32_t faulty_mask,
                             uint32_t order, uint64_t batch, uint64_t* decisions, uint8_t* outcome,
                             ba_counters* counters, uint64_t* witness) {
-    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
     KenumCase g{};
-    int rc = validate_kenum(p, proto, faulty_mask, order, batch, g);
-    if (rc != BA_OK) return rc;
-    if (counters) memset(counters, 0, sizeof *counters);
-    if (witness) *witness = UINT64_MAX;
-    if (batch == 0) return BA_OK;
-    uint64_t wit = UINT64_MAX;
-    HostRun r;
-    r.decisions = decisions, r.outcome = outcome, r.counters = counters, r.tail = &wit;
-    r.chunk_env = "BA_KENUM_HOST_CHUNK";
-    r.chunk = (decisions || outcome) ? kHostChunk : batch;
-    r.queue = [&](const ba_params& q, uint64_t nt, const uint32_t*, const uint8_t*, uint64_t* d_dec,
-                  uint8_t* d_out, void*, uint64_t* d_cnt, hipStream_t st) {
-        return ba_kenum_run_device(ctx, &q, proto, faulty_mask, order, nt, d_dec, d_out, d_cnt,
-                                   d_cnt + BA_NCOUNTERS, st);
-    };
-    rc = host_run(ctx, p, batch, r);
-    if (rc == BA_OK && witness) *witness = wit;
-    return rc;
+    return enum_host_entry(
+        ctx, p, batch, decisions, outcome, counters, witness, "BA_KENUM_HOST_CHUNK",
+        [&] { return validate_kenum(p, proto, faulty_mask, order, batch, g); }, enum_no_prepare,
+        [&](const RunArgs& a, uint64_t* w) { return launch_kenum(a, g, w); });
 }
 
 // ---------------------------------------------------------------------------
@@ -1799,86 +1809,36 @@ extern "C" int ba_smenum_slots(uint32_t form, uint32_t n, uint32_t m, uint32_t f
 static int validate_smenum(const ba_params* p, uint32_t form, uint32_t faulty_mask, uint32_t order,
                            uint64_t batch, SmenumCase& g) {
     if (form > BA_SMENUM_COALITION) return fail(BA_EINVAL, "form=%u", form);
-    int rc = validate_protocol(p, batch, true, true, "the SM enumeration");
+    char prefix[24];
+    snprintf(prefix, sizeof prefix, "form=%u ", form);
+    const uint32_t B = p ? ba_smenum_bits(form, p->n, p->m, faulty_mask) : 0;
+    int rc = validate_enumeration(p, batch, "the SM enumeration", BA_MAX_DEPTH, faulty_mask, order, B, prefix,
+                                  [] { return (int)BA_OK; });
     if (rc != BA_OK) return rc;
-    if (p->faulty_mode != BA_FAULTY_GIVEN || p->order_mode != BA_ORDER_GIVEN)
-        return fail(BA_EINVAL, "faulty_mode=%u order_mode=%u: one given faulty set and order per call "
-                    "(BA_FAULTY_GIVEN, BA_ORDER_GIVEN)", p->faulty_mode, p->order_mode);
-    if (order > BA_OTHER) return fail(BA_EINVAL, "order=%u", order);
-    const uint32_t B = ba_smenum_bits(form, p->n, p->m, faulty_mask);
-    if (B > BA_ENUM_MAX_BITS)
-        return fail(BA_ETOOBIG, "form=%u n=%u m=%u faulty_mask=0x%x: %u free bits > %d", form, p->n,
-                    p->m, faulty_mask, B, BA_ENUM_MAX_BITS);
-    const uint64_t space = 1ull << B;
-    if (p->first_trial > space || batch > space - p->first_trial)
-        return fail(BA_EINVAL, "strategies [%llu, %llu + %llu) reach past 2^%u",
-                    (unsigned long long)p->first_trial, (unsigned long long)p->first_trial,
-                    (unsigned long long)batch, B);
     const SmenumShape s = smenum_shape(form, p->n, p->m, faulty_mask);
     g.form = form, g.n = p->n, g.m = p->m, g.me = s.me, g.fmask = s.F, g.order = order;
     return BA_OK;
 }
 
-// Strategies [first, first + batch) of a case, kEnumLaunchMax per launch (the
-// sink's per-launch sums, at most 31 decisions per strategy, stay below 2^48).
-static int smenum_launch_range(ba_ctx* ctx, const ba_params* p, const SmenumCase& g, uint64_t first,
-                               uint64_t batch, uint64_t* d_decisions, uint8_t* d_outcome,
-                               uint64_t* d_counters, uint64_t* d_witness, void* stream) {
-    ba_params q = *p;
-    for (uint64_t t0 = 0; t0 < batch; t0 += kEnumLaunchMax) {
-        const uint64_t nt = batch - t0 < kEnumLaunchMax ? batch - t0 : kEnumLaunchMax;
-        q.first_trial = first + t0;
-        const RunArgs a = make_args(ctx, &q, nt, nullptr, nullptr, nullptr, nullptr,
-                                    d_decisions ? d_decisions + t0 : nullptr,
-                                    d_outcome ? d_outcome + t0 : nullptr, d_counters, stream);
-        HIP_TRY(launch_smenum(a, g, d_witness));
-    }
-    return BA_OK;
-}
-
-// Nothing is copied from the host: fully asynchronous, and a stream that is
-// capturing a graph takes it.
 extern "C" int ba_smenum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t form,
                                     uint32_t faulty_mask, uint32_t order, uint64_t batch,
                                     uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_counters,
                                     uint64_t* d_witness, void* stream) {
-    return ordered(ctx, stream, [&] {
-        SmenumCase g{};
-        int rc = validate_smenum(p, form, faulty_mask, order, batch, g);
-        if (rc != BA_OK) return rc;
-        if (!d_counters) return fail(BA_EINVAL, "d_counters is required on the device path");
-        if (batch == 0) return BA_OK;
-        return smenum_launch_range(ctx, p, g, p->first_trial, batch, d_decisions, d_outcome, d_counters,
-                                   d_witness, stream);
-    });
+    SmenumCase g{};
+    return enum_device_entry(
+        ctx, p, batch, d_decisions, d_outcome, d_counters, d_witness, stream, nullptr,
+        [&] { return validate_smenum(p, form, faulty_mask, order, batch, g); }, enum_no_prepare,
+        [&](const RunArgs& a, uint64_t* w) { return launch_smenum(a, g, w); });
 }
 
-// Host entry: host_run with no inputs to copy; counters only: one chunk, chunks of
-// kHostChunk strategies when a per-trial output is asked for (the witness
-// min-accumulates across them on the device, in the word after the counters).
 extern "C" int ba_smenum_run(ba_ctx* ctx, const ba_params* p, uint32_t form, uint32_t faulty_mask,
                              uint32_t order, uint64_t batch, uint64_t* decisions, uint8_t* outcome,
                              ba_counters* counters, uint64_t* witness) {
-    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
     SmenumCase g{};
-    int rc = validate_smenum(p, form, faulty_mask, order, batch, g);
-    if (rc != BA_OK) return rc;
-    if (counters) memset(counters, 0, sizeof *counters);
-    if (witness) *witness = UINT64_MAX;
-    if (batch == 0) return BA_OK;
-    uint64_t wit = UINT64_MAX;
-    HostRun r;
-    r.decisions = decisions, r.outcome = outcome, r.counters = counters, r.tail = &wit;
-    r.chunk_env = "BA_SMENUM_HOST_CHUNK";
-    r.chunk = (decisions || outcome) ? kHostChunk : batch;
-    r.queue = [&](const ba_params& q, uint64_t nt, const uint32_t*, const uint8_t*, uint64_t* d_dec,
-                  uint8_t* d_out, void*, uint64_t* d_cnt, hipStream_t st) {
-        return ba_smenum_run_device(ctx, &q, form, faulty_mask, order, nt, d_dec, d_out, d_cnt,
-                                    d_cnt + BA_NCOUNTERS, st);
-    };
-    rc = host_run(ctx, p, batch, r);
-    if (rc == BA_OK && witness) *witness = wit;
-    return rc;
+    return enum_host_entry(
+        ctx, p, batch, decisions, outcome, counters, witness, "BA_SMENUM_HOST_CHUNK",
+        [&] { return validate_smenum(p, form, faulty_mask, order, batch, g); }, enum_no_prepare,
+        [&](const RunArgs& a, uint64_t* w) { return launch_smenum(a, g, w); });
 }
 
 extern "C" int ba_split_votes_device(ba_ctx* ctx, const ba_params* p, uint64_t batch,

@@ -25,18 +25,13 @@
 // place.  What the king of the phase shows (its majority / its x) is worked out
 // first, for the one general k = p - 1, with k's plane picked by uniform selects.
 //
-// All 12 counters come from planes, per lane = word, as in k_enum; the witness is
-// the wave's lowest violating S, one 64-bit atomic min per wave that found one.
-// The lane = trial pick-out of decisions / outcome bytes runs only when asked for,
-// on one-wave blocks that keep the tile's decision planes in LDS.
+// The tile loop, the counters, the witness and the per-trial outputs are the frame
+// of ba_enum_common.hpp; the word evaluator below hands it the lieutenants' planes.
 #include "ba_enum_common.hpp"
 
 #include <utility>
 
 namespace ba {
-
-constexpr int kKenumThreads = 256;
-constexpr uint32_t kKenumBlocksPerCu = 8;
 
 using KCount = Count<5>;  // a tally of at most 16 messages
 
@@ -182,53 +177,28 @@ __device__ __forceinline__ void kenum_king3_phase(const KenumWord& c, uint64_t (
 }
 
 template <int PROTO, int N>
-__global__ __launch_bounds__(kKenumThreads) void k_kenum(KenumCase g, uint64_t first_trial,
-                                                         uint64_t batch,
-                                                         uint64_t* __restrict__ decisions,
-                                                         uint8_t* __restrict__ outcome,
-                                                         uint64_t* __restrict__ counters,
-                                                         unsigned long long* __restrict__ witness,
-                                                         Sink sk) {
+__global__ __launch_bounds__(kEnumThreads) void k_kenum(KenumCase g, uint64_t first_trial,
+                                                        uint64_t batch,
+                                                        uint64_t* __restrict__ decisions,
+                                                        uint8_t* __restrict__ outcome,
+                                                        uint64_t* __restrict__ counters,
+                                                        unsigned long long* __restrict__ witness,
+                                                        Sink sk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char kenum_lds[];
-    constexpr uint32_t n = (uint32_t)N, L = n - 1u;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wpb = blockDim.x >> 6;
-    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
-    const bool want_out = decisions != nullptr || outcome != nullptr;  // then wpb == 1 (launch_kenum)
-    uint64_t* const dec = reinterpret_cast<uint64_t*>(kenum_lds);      // [L][64], want_out only
-
+    constexpr uint32_t n = (uint32_t)N;
     KenumWord c;
     c.F = g.fmask;
     c.nf = (uint32_t)__popc(g.fmask);
     c.ell = n - c.nf;
     c.m = g.m;
     const bool F0 = (g.fmask & 1u) != 0;
-    const uint32_t oc = g.order;
-    const uint64_t ob = oc == 1u ? ~0ull : 0ull;
-    // quorum thresholds (§2.4): every general answers, total = n
-    uint32_t needed = 2u * ((n - 1u) / 3u) + 1u;
-    if (n <= 3u) needed = n - 1u;
-    if (n == 1u) needed = 1u;
-    const uint32_t needA = needed - (oc == 1u ? 1u : 0u);                        // attack iff nA >= needA
-    const int32_t maxN = (int32_t)(L + (oc == 0u ? 1u : 0u)) - (int32_t)needed;  // retreat iff nA <= maxN
+    const uint64_t ob = g.order == 1u ? ~0ull : 0ull;
+    // in-bound is the protocol's
     const bool inb = c.nf <= g.m && n > (PROTO == 0 ? 4u : 3u) * g.m;
-
-    const uint64_t words = (batch + 63u) / 64u, tiles = (words + 63u) / 64u;
-    const uint64_t w0 = first_trial >> 6;
-    const uint32_t nwaves = gridDim.x * wpb, gwave = blockIdx.x * wpb + wv;
-    // per-lane totals: trials, agreement, validity, quorum r / a / u, violations, attack
-    uint64_t tT = 0, tAg = 0, tVa = 0, tQr = 0, tQa = 0, tQu = 0, tVi = 0, tAt = 0;
-    uint64_t wit = ~0ull;
-    for (uint64_t t = gwave; t < tiles; t += nwaves) {
-        const uint64_t lw = t * 64u + lane;  // the lane's word of this call
-        const uint64_t gw = w0 + lw;
-        uint64_t lm = 0;                     // the word's strategies inside the call
-        if (lw < words) {
-            const uint64_t rem = batch - lw * 64u;
-            lm = rem >= 64u ? ~0ull : ((1ull << rem) - 1ull);
-        }
-        c.wlo = (uint32_t)gw;
-        c.whi = (uint32_t)(gw >> 32);
+    const EnumRun run{n, g.fmask, g.order, 0u, inb, first_trial, batch, decisions, outcome, counters, witness};
+    enum_frame<false, true>(run, kenum_lds, sk, [&](uint32_t wlo, uint32_t whi, EnumTally<false>& ty) {
+        c.wlo = wlo;
+        c.whi = whi;
         // round 0: the commander sends
         uint64_t pref[N];
         pref[0] = ob;
@@ -244,90 +214,9 @@ __global__ __launch_bounds__(kKenumThreads) void k_kenum(KenumCase g, uint64_t f
             else kenum_king3_phase<N>(c, pref, p - 1u, base);
         }
         // decisions = the lieutenants' preferences; never undefined
-        uint64_t allA = ~0ull, allR = ~0ull;
-        KCount cA;
-        uint32_t sumA = 0;
 #pragma unroll
-        for (int r = 1; r < N; ++r) {
-            const uint64_t A = pref[r];
-            if (!((c.F >> r) & 1u)) {  // a loyal lieutenant
-                allA &= A;
-                allR &= ~A;
-            }
-            cA.add(A);
-            sumA += (uint32_t)__popcll(A & lm);
-            if (want_out) dec[(uint32_t)(r - 1) * 64u + lane] = A;
-        }
-        const uint64_t agree = allA | allR;
-        const uint64_t valid = F0 ? 0ull : (oc == 1u ? allA : allR);
-        const uint64_t qr = maxN < 0 ? 0ull : ~cA.ge((uint32_t)maxN + 1u);
-        const uint64_t qa = ~qr & cA.ge(needA);
-        const uint64_t viol = lm & ~(agree & (F0 ? ~0ull : valid));
-        tT += (uint32_t)__popcll(lm);
-        tAg += (uint32_t)__popcll(agree & lm);
-        tVa += (uint32_t)__popcll(valid & lm);
-        tQr += (uint32_t)__popcll(qr & lm);
-        tQa += (uint32_t)__popcll(qa & lm);
-        tQu += (uint32_t)__popcll(~qr & ~qa & lm);
-        tAt += sumA;
-        tVi += (uint32_t)__popcll(viol);
-        if (viol) {
-            const uint64_t s = (gw << 6) + (uint64_t)__builtin_ctzll(viol);
-            wit = s < wit ? s : wit;
-        }
-        if (want_out) {
-            // lane = trial: the tile's words one by one out of the decision planes
-            __syncthreads();  // one-wave blocks: the planes are written
-            const uint32_t half = lane >> 5, sh = lane & 31u;
-            for (uint32_t q = 0; q < 64u; ++q) {
-                const uint64_t qw = t * 64u + q;
-                if (qw >= words) break;
-                const uint64_t i = qw * 64u + lane;
-                uint32_t A = 0;
-                for (uint32_t rr = 0; rr < L; ++rr) {
-                    const uint32_t* d = reinterpret_cast<const uint32_t*>(dec + rr * 64u + q);
-                    A |= ((d[half] >> sh) & 1u) << rr;
-                }
-                TrialResult res = trial_result(n, 0, g.fmask, oc, A << 1, 0);
-                res.out = (res.out & ~32u) | (inb ? 32u : 0u);  // in-bound is the protocol's
-                if (i < batch) {
-                    if (decisions) decisions[i] = res.dec;
-                    if (outcome) outcome[i] = (uint8_t)res.out;
-                }
-            }
-            __syncthreads();  // the next tile rewrites the planes
-        }
-    }
-    // wave totals: lane c holds counter c
-    const uint64_t T = enum_wave_sum(tT), Ag = enum_wave_sum(tAg), Va = enum_wave_sum(tVa);
-    const uint64_t Qr = enum_wave_sum(tQr), Qa = enum_wave_sum(tQa), Qu = enum_wave_sum(tQu);
-    const uint64_t Vi = enum_wave_sum(tVi), At = enum_wave_sum(tAt);
-    uint64_t tot[C_NUM];
-    tot[C_TRIALS] = T;
-    tot[C_AGREE] = Ag;
-    tot[C_VAPPL] = F0 ? 0ull : T;  // F, and with it in-bound and the faulty count, is the call's
-    tot[C_VALID] = Va;
-    tot[C_QR] = Qr;
-    tot[C_QA] = Qa;
-    tot[C_QU] = Qu;
-    tot[C_UNDEF] = 0;
-    tot[C_INB] = inb ? T : 0ull;
-    tot[C_VIOL] = inb ? Vi : 0ull;
-    tot[C_FTOT] = (uint64_t)c.nf * T;
-    tot[C_ATT] = At;
-    uint64_t mine = 0;
-#pragma unroll
-    for (int i = 0; i < C_NUM; ++i)
-        if (lane == (uint32_t)i) mine = tot[i];
-    sink_counters(lane, mine, gwave, nwaves, counters, sk);
-    if (witness) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint64_t o = __shfl_xor(wit, off, 64);
-            wit = o < wit ? o : wit;
-        }
-        if (lane == 0 && wit != ~0ull) (void)atomicMin(witness, (unsigned long long)wit);
-    }
+        for (int r = 1; r < N; ++r) ty.put((uint32_t)(r - 1), !((c.F >> r) & 1u), pref[r]);
+    });
 }
 
 using KenumKernel = void (*)(KenumCase, uint64_t, uint64_t, uint64_t*, uint8_t*, uint64_t*,
@@ -339,24 +228,15 @@ static KenumKernel kenum_kernel_of(uint32_t n, std::index_sequence<I...>) {
     return tab[n - 1u];
 }
 
-// One persistent launch: a wave per tile of 64 words (4,096 strategies), at most
-// kKenumBlocksPerCu four-wave blocks per CU; one counter-sink unit per wave.  With
-// per-trial outputs the blocks are one wave each and hold (n - 1) x 64 decision
-// planes in LDS (at most 7.5 KiB).
+// One persistent launch of enum_geometry's shape (at most 7.5 KiB of decision planes).
 hipError_t launch_kenum(const RunArgs& a, const KenumCase& g, uint64_t* witness) {
     if (a.n < 1 || a.n > kKenumMaxN || g.proto > 1 || a.batch == 0 || g.phases < 1 || g.phases > a.n)
         return hipErrorInvalidValue;
-    const bool want_out = a.decisions != nullptr || a.outcome != nullptr;
-    const uint32_t threads = want_out ? 64u : (uint32_t)kKenumThreads, wpb = threads / 64u;
-    const uint32_t lds = want_out ? (a.n - 1u) * 64u * (uint32_t)sizeof(uint64_t) : 0u;
-    const uint64_t words = (a.batch + 63) / 64, tiles = (words + 63) / 64;
-    uint64_t blocks = (tiles + wpb - 1) / wpb;
-    const uint64_t cap = (uint64_t)kKenumBlocksPerCu * a.cu_count * (kKenumThreads / threads);
-    if (blocks > cap) blocks = cap;
+    const EnumGeometry ge = enum_geometry(a, (uint32_t)sizeof(EnumEntry<false>), 0u);
     ProfScope ps(a.prof, "k_kenum", a.stream);
     const KenumKernel k = g.proto == 0 ? kenum_kernel_of<0>(a.n, std::make_index_sequence<kKenumMaxN>{})
                                        : kenum_kernel_of<1>(a.n, std::make_index_sequence<kKenumMaxN>{});
-    hipLaunchKernelGGL(k, dim3((uint32_t)blocks), dim3(threads), lds, a.stream, g, a.first_trial, a.batch,
+    hipLaunchKernelGGL(k, dim3(ge.blocks), dim3(ge.threads), ge.lds, a.stream, g, a.first_trial, a.batch,
                        a.decisions, a.outcome, a.counters, (unsigned long long*)witness, a.sink);
     return hipGetLastError();
 }

@@ -192,6 +192,78 @@ def test_three_ranges_sum_to_the_whole_call(engine, proto, n, F):
         assert {k: whole.counters[k] for k in O.COUNTERS} == message(proto, n, 1, F, o, 0, T)[2]
 
 
+HIGH_FIRST = (1 << 41) | (1 << 33) | (64 * 77)  # a multiple of 64 with bits above 2^32
+
+
+@pytest.mark.parametrize("proto,n,m,F,B,first", [(KING, 9, 2, 0b110000000, 42, 0), (KING3, 7, 1, 0b0001000, 36, 0),
+                                                 (KING, 9, 2, 0b110000000, 42, HIGH_FIRST),
+                                                 (KING, 7, 2, 0b1110000, 36, 1 << 33)])
+def test_persistent_loop_counters_equal_single_pass_shards(engine, proto, n, m, F, B, first):
+    """2^30 strategies in one call are 262,144 tiles: every wave of the grid (at most
+    eight four-wave blocks per CU) takes tile after tile and carries its totals and its
+    witness across them.  Thirty-two shards of 2^25 strategies (8,192 tiles, 2,048 blocks:
+    one tile per wave on a 256-CU device) sum to the same counters, and the call's
+    witness is the smallest of theirs.  The first three cases are in bound; KING (7,2)
+    with three traitors is not: there a witness, if any, must lie in the range."""
+    from ba_amd import lib as L
+    assert L.kenum_bits(proto, n, m, F) == B
+    T, K = 1 << 30, 32
+    whole = engine.run_kenum(proto, n, m, F, A, first=first, count=T)
+    parts = [engine.run_kenum(proto, n, m, F, A, first=first + i * (T // K), count=T // K) for i in range(K)]
+    assert whole.counters == {k: sum(p.counters[k] for p in parts) for k in whole.counters}
+    wits = [p.witness for p in parts if p.witness is not None]
+    assert whole.witness == (min(wits) if wits else None)
+    c = whole.counters
+    assert c["trials"] == T
+    clean = c["agreement"] == T and c["validity"] == c["validity_applicable"]
+    assert (whole.witness is None) == clean
+    if (proto, n) == (KING, 7):
+        assert c["in_bound"] == 0 and (clean or first <= whole.witness < first + T)
+    else:
+        assert c["in_bound"] == T and c["bound_violations"] == 0 and clean
+
+
+def test_persistent_loop_with_outputs_equals_single_pass_shards(engine):
+    """With per-trial outputs the blocks are one wave each, at most 32 per CU.  One device
+    call of 2^26 + 4,096 + 229 strategies is 16,386 tiles, so blocks take a second and a
+    third tile and reuse their decision planes in LDS; the same range as calls of 2^24
+    (4,096 tiles each: one tile per block) gives the same bytes, counters and witness, and
+    the range's two ends (a whole tile; a tile and a partial word) equal the model."""
+    import torch
+    from ba_amd import lib as L
+    proto, n, m, F, o, first = KING3, 7, 1, 0b0001000, A, 1 << 35
+    assert L.kenum_bits(proto, n, m, F) == 36
+    T, S = (1 << 26) + 4096 + 229, 1 << 24
+    s = torch.cuda.current_stream().cuda_stream
+
+    def run(lo, count, dec, out, cnt, wit):
+        engine.run_kenum_device(L.make_params(n, m, first_trial=first + lo), proto, F, o, count,
+                                d_decisions=dec[lo:].data_ptr(), d_outcome=out[lo:].data_ptr(),
+                                d_counters=cnt.data_ptr(), d_witness=wit.data_ptr(), stream=s)
+
+    bufs = []
+    for shard in (T, S):
+        dec = torch.full((T,), -1, dtype=torch.int64, device="cuda")
+        out = torch.full((T,), 255, dtype=torch.uint8, device="cuda")
+        cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
+        wit = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+        for lo in range(0, T, shard):
+            run(lo, min(shard, T - lo), dec, out, cnt, wit)
+        torch.cuda.synchronize()
+        bufs.append((dec, out, cnt, wit))
+    (dec, out, cnt, wit), ref = bufs
+    assert torch.equal(dec, ref[0]) and torch.equal(out, ref[1])
+    assert torch.equal(cnt, ref[2]) and torch.equal(wit, ref[3])
+    assert int(cnt[0]) == T and cnt.cpu().tolist()[12:] == [0, 0, 0, 0]
+    for lo, count in ((0, 4096), (T - 4096 - 229, 4096 + 229)):
+        mdec, mout, _, _ = message(proto, n, m, F, o, first + lo, count)
+        same(dec[lo:lo + count].cpu().numpy().view(np.uint64), mdec, f"decisions at {lo}")
+        same(out[lo:lo + count].cpu().numpy(), mout, f"outcome at {lo}")
+    c = dict(zip(L.COUNTER_NAMES, cnt.cpu().tolist()))
+    clean = c["agreement"] == T and c["validity"] == c["validity_applicable"]
+    assert (int(wit.cpu().numpy().view(np.uint64)[0]) == L.NO_WITNESS) == clean
+
+
 def test_host_chunks_give_identical_outputs(engine, monkeypatch):
     first, count = 64 * 2, 64 * 9 + 17
     ref = message(KING3, 3, 1, 0b001, A, first, count)

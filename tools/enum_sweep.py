@@ -32,10 +32,11 @@ import json
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "byzantine-agreement_amd"))
+
+from enum_common import run_case as walk, time_alternating  # noqa: E402
 
 
 def classes(n, f):
@@ -49,32 +50,11 @@ def classes(n, f):
 
 
 def run_case(eng, L, torch, n, m, F, o, args):
-    B = L.enum_bits(n, m, F)
-    total = 1 << B
-    cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
-    wit = torch.full((1,), -1, dtype=torch.int64, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    done, secs, calls, slowest = 0, 0.0, 0, 0.0
-    while done < total:
-        nt = min(args.chunk, total - done)
-        t0 = time.perf_counter()
-        eng.run_enum_device(L.make_params(n, m, first_trial=done), F, o, nt, d_counters=cnt.data_ptr(),
-                            d_witness=wit.data_ptr(), stream=s)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        done += nt
-        secs += dt
-        calls += 1
-        slowest = max(slowest, dt)
-        if dt > args.call_limit or secs > args.case_budget:
-            break
-    c = dict(zip(L.COUNTER_NAMES, cnt.cpu().tolist()))
-    w = int(wit.cpu().numpy().view("uint64")[0])
-    return {"n": n, "m": m, "faulty_mask": F, "order": o, "bits": B, "strategies": total,
-            "covered": done, "complete": done == total, "counters": c,
-            "witness": None if w == L.NO_WITNESS else w, "calls": calls,
-            "seconds": round(secs, 4), "slowest_call_s": round(slowest, 4),
-            "strategies_per_s": float(f"{done / secs:.4e}") if secs > 0 else None}
+    def call(first, count, d_cnt, d_wit, stream):
+        eng.run_enum_device(L.make_params(n, m, first_trial=first), F, o, count, d_counters=d_cnt,
+                            d_witness=d_wit, stream=stream)
+
+    return walk(call, L, torch, {"n": n, "m": m, "faulty_mask": F, "order": o}, L.enum_bits(n, m, F), args)
 
 
 def sweep(args):
@@ -120,21 +100,9 @@ def time_enum(args):
             eng.run_adv_device(p, T, L.ADV_SPLIT, d_faulty=fm.data_ptr(), d_order=oc.data_ptr(),
                                d_counters=cnt.data_ptr(), stream=s)
 
-        kernels = (("k_enum", enum), ("k_adv", adv))
-        for _, fn in kernels:  # warm-up
-            fn()
-        torch.cuda.synchronize()
-        ms = {name: [] for name, _ in kernels}
-        for _ in range(args.repeats):  # the kernels alternate run by run
-            for name, fn in kernels:
-                eng.profile(True)
-                fn()
-                torch.cuda.synchronize()
-                launches, total = eng.profile_read()[name]
-                assert launches == 1
-                ms[name].append(total)
-        eng.profile(False)
-        for name, _ in kernels:
+        kernels = (("k_enum", "k_enum", enum), ("k_adv", "k_adv", adv))
+        ms = time_alternating(eng, torch, kernels, args.repeats)
+        for name, _, _ in kernels:
             med = statistics.median(ms[name])
             print(json.dumps({"kernel": name + (" split, staged GIVEN inputs" if name == "k_adv" else ""),
                               "n": n, "m": m, "faulty_mask": F, "order": o, "trials": T,

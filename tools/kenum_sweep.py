@@ -34,10 +34,11 @@ import json
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "byzantine-agreement_amd"))
+
+from enum_common import run_case as walk, time_alternating  # noqa: E402
 
 PROTOS = {"king": 0, "king3": 1}
 
@@ -57,32 +58,12 @@ def classes(n, P, f):
 
 
 def run_case(eng, L, torch, proto, n, m, F, o, args):
-    B = L.kenum_bits(proto, n, m, F)
-    total = 1 << B
-    cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
-    wit = torch.full((1,), -1, dtype=torch.int64, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    done, secs, calls, slowest = 0, 0.0, 0, 0.0
-    while done < total:
-        nt = min(args.chunk, total - done)
-        t0 = time.perf_counter()
-        eng.run_kenum_device(L.make_params(n, m, first_trial=done), proto, F, o, nt,
-                             d_counters=cnt.data_ptr(), d_witness=wit.data_ptr(), stream=s)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        done += nt
-        secs += dt
-        calls += 1
-        slowest = max(slowest, dt)
-        if dt > args.call_limit or secs > args.case_budget:
-            break
-    c = dict(zip(L.COUNTER_NAMES, cnt.cpu().tolist()))
-    w = int(wit.cpu().numpy().view("uint64")[0])
-    return {"proto": args.proto, "n": n, "m": m, "faulty_mask": F, "order": o, "bits": B,
-            "strategies": total, "covered": done, "complete": done == total, "counters": c,
-            "witness": None if w == L.NO_WITNESS else w, "calls": calls,
-            "seconds": round(secs, 4), "slowest_call_s": round(slowest, 4),
-            "strategies_per_s": float(f"{done / secs:.4e}") if secs > 0 else None}
+    def call(first, count, d_cnt, d_wit, stream):
+        eng.run_kenum_device(L.make_params(n, m, first_trial=first), proto, F, o, count, d_counters=d_cnt,
+                             d_witness=d_wit, stream=stream)
+
+    head = {"proto": args.proto, "n": n, "m": m, "faulty_mask": F, "order": o}
+    return walk(call, L, torch, head, L.kenum_bits(proto, n, m, F), args)
 
 
 def sweep(args):
@@ -132,19 +113,7 @@ def time_kenum(args):
                                  d_counters=cnt.data_ptr(), stream=s)
 
         kernels = (("k_kenum", kenum, S), ("k_king3", king3, T))
-        for _, fn, _ in kernels:  # warm-up
-            fn()
-        torch.cuda.synchronize()
-        ms = {name: [] for name, _, _ in kernels}
-        for _ in range(args.repeats):  # the kernels alternate run by run
-            for name, fn, _ in kernels:
-                eng.profile(True)
-                fn()
-                torch.cuda.synchronize()
-                launches, total = eng.profile_read()[name]
-                assert launches == 1
-                ms[name].append(total)
-        eng.profile(False)
+        ms = time_alternating(eng, torch, [(name, name, fn) for name, fn, _ in kernels], args.repeats)
         per = {}
         for name, _, count in kernels:
             med = statistics.median(ms[name])

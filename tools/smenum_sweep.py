@@ -36,10 +36,11 @@ import json
 import os
 import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "byzantine-agreement_amd"))
+
+from enum_common import run_case as walk, time_alternating  # noqa: E402
 
 FORMS = {"messages": 0, "coalition": 1}
 
@@ -64,33 +65,15 @@ def emit(args, row):
 
 
 def run_case(eng, L, torch, form, n, m, F, o, args):
-    B = L.smenum_bits(form, n, m, F)
-    total = 1 << B
-    cnt = torch.zeros(16, dtype=torch.int64, device="cuda")
-    wit = torch.full((1,), -1, dtype=torch.int64, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    done, secs, calls, slowest = 0, 0.0, 0, 0.0
-    while done < total:
-        nt = min(args.chunk, total - done)
-        t0 = time.perf_counter()
-        eng.run_smenum_device(L.make_params(n, m, first_trial=done), form, F, o, nt,
-                              d_counters=cnt.data_ptr(), d_witness=wit.data_ptr(), stream=s)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        done += nt
-        secs += dt
-        calls += 1
-        slowest = max(slowest, dt)
-        if dt > args.call_limit or secs > args.case_budget:
-            break
-    c = dict(zip(L.COUNTER_NAMES, cnt.cpu().tolist()))
-    w = int(wit.cpu().numpy().view("uint64")[0])
-    return {"form": [k for k, v in FORMS.items() if v == form][0], "n": n, "m": m, "faulty_mask": F,
-            "order": o, "bits": B, "strategies": total, "covered": done, "complete": done == total,
-            "counters": c, "witness": None if w == L.NO_WITNESS else w,
-            "witness_messages": None if w == L.NO_WITNESS else L.decode_smstrategy(form, n, m, F, o, w),
-            "calls": calls, "seconds": round(secs, 4), "slowest_call_s": round(slowest, 4),
-            "strategies_per_s": float(f"{done / secs:.4e}") if secs > 0 else None}
+    def call(first, count, d_cnt, d_wit, stream):
+        eng.run_smenum_device(L.make_params(n, m, first_trial=first), form, F, o, count, d_counters=d_cnt,
+                              d_witness=d_wit, stream=stream)
+
+    def messages(w):
+        return {"witness_messages": None if w is None else L.decode_smstrategy(form, n, m, F, o, w)}
+
+    head = {"form": [k for k, v in FORMS.items() if v == form][0], "n": n, "m": m, "faulty_mask": F, "order": o}
+    return walk(call, L, torch, head, L.smenum_bits(form, n, m, F), args, messages)
 
 
 def sweep(args):
@@ -147,19 +130,7 @@ def time_smenum(args):
 
         kernels = (("k_smenum coalition", "k_smenum", smenum(sm_c), sm_c),
                    ("k_smenum messages", "k_smenum", smenum(sm_m), sm_m), ("k_kenum KING", "k_kenum", kenum, kk))
-        for _, _, fn, _ in kernels:  # warm-up
-            fn()
-        torch.cuda.synchronize()
-        ms = {what: [] for what, _, _, _ in kernels}
-        for _ in range(args.repeats):  # the kernels alternate run by run
-            for what, name, fn, _ in kernels:
-                eng.profile(True)
-                fn()
-                torch.cuda.synchronize()
-                launches, total = eng.profile_read()[name]
-                assert launches == 1
-                ms[what].append(total)
-        eng.profile(False)
+        ms = time_alternating(eng, torch, [(what, name, fn) for what, name, fn, _ in kernels], args.repeats)
         for what, _, _, (_, n, m, F) in kernels:
             med = statistics.median(ms[what])
             emit(args, {"kernel": what, "n": n, "m": m, "faulty_mask": F, "order": o, "strategies": S,
