@@ -32,6 +32,9 @@ SPLIT_FIRST_HOP, SPLIT_SECOND_HOP = 1, 2
 ADV_SPLIT, ADV_FLIP, ADV_ANTI = 0, 1, 2  # scripted traitor policies (docs/SEMANTICS.md §7)
 KING_COIN, KING_SPLIT = 0, 1  # Phase King's and KING3's faulty senders (docs/SEMANTICS.md §9, §10)
 KING_UNSETTLED = 255  # RunResult.settled: the loyal generals differ after the last phase
+RAND_LOCAL, RAND_COMMON = 0, 1  # run_rand's coin: each general's own, or one per trial (docs/SEMANTICS.md §13)
+RAND_MAX_PHASES = 64
+RAND_UNDECIDED, RAND_UNSAFE = 255, 254  # RunResult.decided beside a phase number 1..R
 COUNTER_NAMES = ["trials", "agreement", "validity_applicable", "validity", "quorum_retreat",
                  "quorum_attack", "quorum_undetermined", "undefined_decisions", "in_bound",
                  "bound_violations", "faulty_total", "attack_decisions"]
@@ -53,6 +56,7 @@ EXPORTS = ["ba_version", "ba_device_count", "ba_ctx_create", "ba_ctx_destroy", "
            "ba_king_run_trials", "ba_king_run_trials_device", "ba_king_coin_calls",
            "ba_king_phases", "ba_king3_run_trials", "ba_king3_run_trials_device",
            "ba_king3_coin_calls", "ba_king3_phases",
+           "ba_rand_run_trials", "ba_rand_run_trials_device", "ba_rand_coin_calls",
            "ba_kenum_bits", "ba_kenum_slots", "ba_kenum_run", "ba_kenum_run_device",
            "ba_smenum_bits", "ba_smenum_slots", "ba_smenum_run", "ba_smenum_run_device"]
 KENUM_KING, KENUM_KING3 = 0, 1  # the protocol of run_kenum (docs/SEMANTICS.md §11)
@@ -212,6 +216,12 @@ def load(path: str | None = None):
     lib.ba_king3_coin_calls.restype = u64
     lib.ba_king3_phases.argtypes = [u32, u32]
     lib.ba_king3_phases.restype = u32
+    lib.ba_rand_run_trials.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u32, u64, vp, vp, vp, vp,
+                                       vp, ctypes.POINTER(Counters)]
+    lib.ba_rand_run_trials_device.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u32, u64, vp, vp,
+                                              vp, vp, vp, vp, vp]
+    lib.ba_rand_coin_calls.argtypes = [u32, u32, u32]
+    lib.ba_rand_coin_calls.restype = u64
     lib.ba_kenum_bits.argtypes = [u32, u32, u32, u32]
     lib.ba_kenum_bits.restype = u32
     lib.ba_kenum_slots.argtypes = [u32, u32, u32, u32, vp, vp, vp, vp, u32]
@@ -277,6 +287,7 @@ class RunResult:
     vsets: np.ndarray | None = None  # run_sm(want_vsets=True): bits 2(r-1) attack, 2(r-1)+1 retreat in V_r
     witness: int | None = None  # run_enum: the smallest violating strategy, None when there is none
     settled: np.ndarray | None = None  # run_king / run_king3(want_settled=True): phase from which the loyal agree, 255 = never
+    decided: np.ndarray | None = None  # run_rand(want_decided=True): phase by which every loyal general decided, 255 = not within R, 254 = unsafe
 
     def decision(self, t: int, r: int) -> int:
         """Decision code of lieutenant r (1..n-1) in trial t."""
@@ -436,6 +447,30 @@ class Engine:
             self.handle, ctypes.byref(params), policy, batch, d_faulty or None, d_order or None,
             d_decisions or None, d_outcome or None, d_settled or None, d_counters or None,
             stream or None))
+
+    def run_rand(self, n, m, batch, phases, policy=KING_COIN, coin=RAND_COMMON, seed=0,
+                 lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN, f=0, order_mode=ORDER_GIVEN,
+                 order_value=ATTACK, engine=ENGINE_AUTO, first_trial=0, faulty=None, order=None,
+                 want_decisions=True, want_outcome=True, want_decided=False) -> RunResult:
+        """Resolve `batch` trials of randomized agreement (Ben-Or rounds, `phases` of them;
+        coin RAND_LOCAL / RAND_COMMON, policy KING_COIN / KING_SPLIT; docs/SEMANTICS.md §13;
+        m <= 10) through host buffers; the same inputs as `run` and `run_king3` with equal
+        keywords."""
+        params = (n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, engine, first_trial)
+        dec, out, cnt, dcd = self._run_protocol(self.lib.ba_rand_run_trials, (policy, coin, phases), params,
+                                                batch, faulty, order, want_decisions, want_outcome,
+                                                (np.uint8, want_decided))
+        return RunResult(dec, out, cnt, decided=dcd)
+
+    def run_rand_device(self, params: Params, batch: int, phases: int, policy: int = KING_COIN,
+                        coin: int = RAND_COMMON, d_faulty=0, d_order=0, d_decisions=0, d_outcome=0,
+                        d_decided=0, d_counters=0, stream=0):
+        """Enqueue randomized-agreement trials on device pointers (ba_rand_run_trials_device);
+        asynchronous, counters accumulated."""
+        _check(self.lib, self.lib.ba_rand_run_trials_device(
+            self.handle, ctypes.byref(params), policy, coin, phases, batch, d_faulty or None,
+            d_order or None, d_decisions or None, d_outcome or None, d_decided or None,
+            d_counters or None, stream or None))
 
     def _run_enum(self, fn, bits, lead, n, m, faulty_mask, order, first, count, want_decisions, want_outcome,
                   lie_mode, faulty_mode, order_mode, engine) -> RunResult:
@@ -794,6 +829,12 @@ def king3_coin_calls(n: int, m: int) -> int:
     """Philox calls per 64-trial word of k_king3 when every sender is faulty in the word
     (ba_king3_coin_calls)."""
     return int(load().ba_king3_coin_calls(n, m))
+
+
+def rand_coin_calls(n: int, phases: int, coin: int) -> int:
+    """Philox calls per 64-trial word of k_rand when every sender is faulty in the word and
+    every toss is drawn (ba_rand_coin_calls); 0 for bad arguments."""
+    return int(load().ba_rand_coin_calls(n, phases, coin))
 
 
 def king3_phases(n: int, m: int) -> int:

@@ -227,6 +227,13 @@ hipError_t launch_king(const RunArgs& a, uint32_t policy, uint32_t phases, uint8
 constexpr uint32_t kKing3MaxM = 10;
 hipError_t launch_king3(const RunArgs& a, uint32_t policy, uint32_t phases, uint8_t* settled);
 
+// Randomized agreement (ba_rand.hip, docs/SEMANTICS.md §13): KING3's arguments and
+// limit on a.m; coin: BA_RAND_*; phases = R, 1..kRandMaxPhases, run in full unless
+// a word finishes early.  decided optional.
+constexpr uint32_t kRandMaxPhases = 64;
+hipError_t launch_rand(const RunArgs& a, uint32_t policy, uint32_t coin, uint32_t phases,
+                       uint8_t* decided);
+
 // Phase King and KING3 against every traitor strategy of one case (ba_kenum.hip,
 // docs/SEMANTICS.md §11): trial t is strategy S = t.  Everything the kernel needs
 // is in the case: no map, no upload.  n is a template parameter of k_kenum (the

@@ -22,8 +22,9 @@
 //   part[p][l]      plane p of lane l's tally, read back by lane l ^ 32; the two
 //                   tallies of the propose round pass through it one after the other
 //   kx, agr         the king's x plane; the loyal attack / retreat holders of `settled`
-// The King helpers are ba_king_common.hpp's, shared with k_king; the wave
-// helpers ba_wave_proto.hpp's.
+// The King helpers are ba_king_common.hpp's, shared with k_king; so is the walk
+// over the sender pairs of the value and propose rounds (king3_round, king3_merge),
+// which k_rand takes too.  The wave helpers are ba_wave_proto.hpp's.
 //
 // The three wave-uniform shortcuts of k_king hold here too, invisible in the
 // results: a group of calls none of whose senders is faulty in a trial of the
@@ -35,7 +36,6 @@ namespace ba {
 
 constexpr uint32_t kKing3Tag = 192;   // Philox ctr word 1 of round q: kKing3Tag + q
 constexpr int kKing3Threads = 256;    // four independent waves
-constexpr int kKing3PartPlanes = 5;   // a slice counts at most 16 messages
 
 struct King3Wave {
     uint64_t F[kMaxN];
@@ -45,131 +45,6 @@ struct King3Wave {
     uint64_t kx;
     uint64_t agr[2];
 };
-
-using Tally3 = Count<kKing3PartPlanes>;
-
-// a group's count (four digits, up to 8) added into a slice's tally
-__device__ __forceinline__ void king3_tally_add(Tally3& tally, const uint64_t (&digit)[4]) {
-    uint64_t carry = 0;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const uint64_t t = tally.c[p];
-        tally.c[p] = xor3(t, digit[p], carry);
-        carry = maj3(t, digit[p], carry);
-    }
-    tally.c[4] ^= carry;
-    static_assert(kKing3PartPlanes == 5, "a slice's tally: up to 16 messages");
-}
-
-// One group of G sender pairs of a value round (PROP = false) or a propose round
-// (PROP = true): this lane's pairs are u = v0 + 2 g + s.  The value round adds the
-// 2 G votes general i is shown into t1 (own = its preference plane, read from
-// s.pref); the propose round adds the attack proposals it is shown into t1 and the
-// retreat proposals into t0 (own1 / own0 = its own proposal planes; the senders'
-// are s.pa and s.pr), both from one draw: a faulty sender's coin is its attack
-// proposal, the complement its retreat proposal.
-template <bool COIN, int G, bool PROP>
-__device__ __forceinline__ void king3_group(const King3Wave& s, uint32_t i, uint32_t sl, uint32_t v0,
-                                            uint32_t n, uint32_t npairs, uint32_t q, uint64_t gw,
-                                            uint64_t seed, uint64_t own1, uint64_t own0, Tally3& t1,
-                                            Tally3& t0) {
-    const uint32_t odd = i & 1u;
-    // Before the draw only what decides it is loaded (the senders' planes come
-    // after it: held across the calls they cost registers).
-    uint32_t ja[G];
-    bool act[G], need = false;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const uint32_t u = v0 + 2u * (uint32_t)g + sl;  // <= 15: senders 2u, 2u + 1 <= 31
-        act[g] = u < npairs;
-        ja[g] = 2u * (act[g] ? u : 0u);
-        // the lane's own call is sender ja + odd's; it serves recipients i and i ^ 1
-        need |= act[g] && s.F[ja[g] + odd] != 0 && (i & ~1u) < n;
-    }
-    uint64_t ca[G], cb[G];  // what a faulty sender 2u / 2u + 1 shows recipient i
-#pragma unroll
-    for (int g = 0; g < G; ++g) ca[g] = cb[g] = odd ? ~0ull : 0ull;  // BA_KING_SPLIT: r & 1
-    if constexpr (COIN) {
-        if (__ballot(need) != 0) {
-            const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-            P4 c[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-                c[g] = P4{16u * (ja[g] + odd) + (i >> 1), kKing3Tag + q, (uint32_t)gw, (uint32_t)(gw >> 32)};
-            if constexpr (G == 1) c[0] = philox10(c[0], k0, k1);
-            else philox10_n<G>(c, k0, k1);
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const KingCoin h = king_halves(c[g], odd);
-                const uint64_t got = swap_neighbour(h.give);
-                ca[g] = odd ? got : h.keep;
-                cb[g] = odd ? h.keep : got;
-            }
-        }
-    }
-    // the group's 2 G <= 8 messages carry-saved in compile-time order, then the
-    // count's four digits added to the tally once
-    const uint64_t* src1 = PROP ? s.pa : s.pref;
-    Csa<4> v1, v0s;
-    static_for_h<0, G>([&](auto gi) {
-        constexpr int g = gi();
-        // an inactive pair sends nothing; a general counts its own true message
-        const uint64_t Fa = s.F[ja[g]], Fb = s.F[ja[g] + 1];
-        const bool sa = ja[g] == i, sb = ja[g] + 1 == i;
-        uint64_t ma = sa ? own1 : (src1[ja[g]] & ~Fa) | (Fa & ca[g]);
-        uint64_t mb = sb ? own1 : (src1[ja[g] + 1] & ~Fb) | (Fb & cb[g]);
-        if (!act[g]) ma = mb = 0;
-        v1.template add<2 * g>(ma);
-        v1.template add<2 * g + 1>(mb);
-        if constexpr (PROP) {
-            uint64_t ra = sa ? own0 : (s.pr[ja[g]] & ~Fa) | (Fa & ~ca[g]);
-            uint64_t rb = sb ? own0 : (s.pr[ja[g] + 1] & ~Fb) | (Fb & ~cb[g]);
-            if (!act[g]) ra = rb = 0;
-            v0s.template add<2 * g>(ra);
-            v0s.template add<2 * g + 1>(rb);
-        }
-    });
-    uint64_t digit[4];
-    v1.template resolve<0, 2 * G, false>(digit, 0);
-    king3_tally_add(t1, digit);
-    if constexpr (PROP) {
-        v0s.template resolve<0, 2 * G, false>(digit, 0);
-        king3_tally_add(t0, digit);
-    }
-}
-
-// All sender pairs of one round, in groups of at most G pairs per lane.
-template <bool COIN, bool PROP>
-__device__ __forceinline__ void king3_round(const King3Wave& s, uint32_t i, uint32_t sl, uint32_t n,
-                                            uint32_t npairs, uint32_t q, uint64_t gw, uint64_t seed,
-                                            uint64_t own1, uint64_t own0, Tally3& t1, Tally3& t0) {
-    for (uint32_t v0 = 0; v0 < npairs; v0 += 8) {
-        const uint32_t left = npairs - v0;  // pairs of both slices: groups of ceil(left / 2)
-        if (left > 6) king3_group<COIN, 4, PROP>(s, i, sl, v0, n, npairs, q, gw, seed, own1, own0, t1, t0);
-        else if (left > 4) king3_group<COIN, 3, PROP>(s, i, sl, v0, n, npairs, q, gw, seed, own1, own0, t1, t0);
-        else if (left > 2) king3_group<COIN, 2, PROP>(s, i, sl, v0, n, npairs, q, gw, seed, own1, own0, t1, t0);
-        else king3_group<COIN, 1, PROP>(s, i, sl, v0, n, npairs, q, gw, seed, own1, own0, t1, t0);
-    }
-}
-
-// The two slices' tallies of general i merged through s.part: six planes, up to 32.
-__device__ __forceinline__ Count<kKing3PartPlanes + 1> king3_merge(King3Wave& s, uint32_t lane,
-                                                                   const Tally3& tally) {
-    wave_sync();  // the previous merge has read part
-#pragma unroll
-    for (int b = 0; b < kKing3PartPlanes; ++b) s.part[b][lane] = tally.c[b];
-    wave_sync();
-    Count<kKing3PartPlanes + 1> c;
-    uint64_t carry = 0;
-#pragma unroll
-    for (int b = 0; b < kKing3PartPlanes; ++b) {
-        const uint64_t o = s.part[b][lane ^ 32u];
-        c.c[b] = xor3(tally.c[b], o, carry);
-        carry = maj3(tally.c[b], o, carry);
-    }
-    c.c[kKing3PartPlanes] = carry;
-    return c;
-}
 
 template <bool GEN, bool COIN>
 __global__ __launch_bounds__(kKing3Threads) void k_king3(uint32_t n, uint32_t m, uint32_t phases,
@@ -225,7 +100,7 @@ __global__ __launch_bounds__(kKing3Threads) void k_king3(uint32_t n, uint32_t m,
             uint64_t A, R;
             {
                 Tally3 tv, unused;
-                king3_round<COIN, false>(s, i, sl, n, npairs, 3 * p - 2, gw, seed, pref, 0, tv, unused);
+                king3_round<kKing3Tag, COIN, false>(s, i, sl, n, npairs, 3 * p - 2, gw, seed, pref, 0, tv, unused);
                 const auto c1 = king3_merge(s, lane, tv);
                 R = ~c1.ge(Tm);  // c0 >= n - m  <=>  c1 <= m
                 A = c1.ge(Tq) & ~R;  // retreat wins when both hold (n <= 2m)
@@ -240,7 +115,7 @@ __global__ __launch_bounds__(kKing3Threads) void k_king3(uint32_t n, uint32_t m,
             uint64_t x, sure;
             {
                 Tally3 ta, tr;
-                king3_round<COIN, true>(s, i, sl, n, npairs, 3 * p - 1, gw, seed, A, R, ta, tr);
+                king3_round<kKing3Tag, COIN, true>(s, i, sl, n, npairs, 3 * p - 1, gw, seed, A, R, ta, tr);
                 const auto d1 = king3_merge(s, lane, ta);
                 const uint64_t x1 = d1.ge(Tm), s1 = d1.ge(Tq);
                 const auto d0 = king3_merge(s, lane, tr);

@@ -447,6 +447,64 @@ uint64_t ba_king3_coin_calls(uint32_t n, uint32_t m);  /* host only */
 /* P = min(m, n-1) + 1; 0 for n outside 1..32 or m > 10. */
 uint32_t ba_king3_phases(uint32_t n, uint32_t m);      /* host only */
 
+/* ---- RAND: randomized agreement, Ben-Or rounds with a local or a common coin -----
+ * Ben-Or's protocol in Bracha's threshold form (docs/SEMANTICS.md §13; no ba.py
+ * analogue): KING3's setting, participants, faulty stance, adversaries and epilogue,
+ * no king, R phases chosen by the caller (1..BA_RAND_MAX_PHASES), and agreement with
+ * probability 1 rather than after m+1 phases.  Every general also keeps a sticky
+ * flag D ("decided") and the value V it decided.
+ *   round 0      as Phase King's;
+ *   phase p      Report (q = 3p-2): everyone sends its preference x; general i counts
+ *                the attack votes c1 of all n generals (its own true value included),
+ *                c0 = n - c1, and will propose attack if 2 c1 > n+m, else retreat if
+ *                2 c0 > n+m, else nothing.  Propose (q = 3p-1): everyone shows its
+ *                proposal (a faulty sender always shows a value); i counts d0 and d1,
+ *                v = retreat if d0 > m, else attack if d1 > m, else none; where v
+ *                exists x = v, and if also 2 d_v > n+m and D is clear, D = 1, V = v.
+ *                Toss (q = 3p): where v is none, x = i's coin of the phase:
+ *                BA_RAND_LOCAL its own c(3p, 33 i), BA_RAND_COMMON the one coin
+ *                c(3p, 0) of the trial, an ideal common coin the protocol assumes;
+ *   decision     lieutenant r decides its x after phase R (never undefined), then the
+ *                quorum and the IC1/IC2 flags as everywhere else.
+ * A faulty sender j shows recipient r != j, in rounds 0, 3p-2 and 3p-1, under
+ *   BA_KING_COIN   c(q, 32 j + r), where c(q, x) = coin(256 + q, x) of the OM lie stream;
+ *   BA_KING_SPLIT  r & 1 (no message coin is drawn; the tosses still are).
+ * Neither sees the coin, neither is the worst case.  In-bound means |F| <= m and
+ * n > 3m.  BA_C_BOUND_VIOL therefore counts in-bound trials still split (or invalid)
+ * after R phases: non-termination within R, which has a probability, not a safety
+ * failure.  Safety is what decided[t] (optional, uint8) reports, by precedence:
+ *   BA_RAND_UNSAFE     at the end of some phase two loyal generals with D set held
+ *                      different V, or a loyal general with D set had x != V, or the
+ *                      commander was loyal and a loyal general's V was not its order;
+ *   p in 1..R          the first phase at whose end every loyal general (a loyal
+ *                      commander included) has D set; 1 when nobody is loyal;
+ *   BA_RAND_UNDECIDED  neither.
+ * In bound BA_RAND_UNSAFE never appears.  p->m <= 10, p->lie_mode BA_LIE_PHILOX (TABLE:
+ * BA_ENOTSUP), p->engine BA_ENGINE_AUTO, policy <= BA_KING_SPLIT, coin <=
+ * BA_RAND_COMMON, phases in 1..BA_RAND_MAX_PHASES (else BA_EINVAL); every faulty/order
+ * mode, first_trial and seed as in ba_run_trials, and the synthetic inputs are
+ * ba_run_trials' own.  decisions / outcome / counters: the layouts above. */
+#define BA_RAND_LOCAL 0
+#define BA_RAND_COMMON 1
+#define BA_RAND_MAX_PHASES 64
+#define BA_RAND_UNDECIDED 255
+#define BA_RAND_UNSAFE 254
+int ba_rand_run_trials(struct ba_ctx* ctx, const ba_params* p, uint32_t policy, uint32_t coin,
+                       uint32_t phases, uint64_t batch, const uint32_t* faulty_mask,
+                       const uint8_t* order, uint64_t* decisions, uint8_t* outcome,
+                       uint8_t* decided, ba_counters* counters);   /* counters overwritten */
+/* The same phases on device buffers, enqueued on `stream` in the ctx's call order
+ * (NULL = HIP's null stream). */
+int ba_rand_run_trials_device(struct ba_ctx* ctx, const ba_params* p, uint32_t policy,
+                              uint32_t coin, uint32_t phases, uint64_t batch,
+                              const uint32_t* d_faulty_mask, const uint8_t* d_order,
+                              uint64_t* d_decisions, uint8_t* d_outcome, uint8_t* d_decided,
+                              uint64_t* d_counters, void* stream);   /* accumulated, async */
+/* ceil(n/2) (1 + 2 n R) + R (LOCAL ? n : 1): Philox calls per 64-trial word when every
+ * sender is faulty somewhere in the word and every toss is drawn.  0 for n outside
+ * 1..32, phases outside 1..64 or coin > 1. */
+uint64_t ba_rand_coin_calls(uint32_t n, uint32_t phases, uint32_t coin);  /* host only */
+
 /* ---- Phase King and KING3 against every traitor strategy of one case -----------
  * BA_KING_COIN and BA_KING_SPLIT are two adversaries; the theorems (agreement whenever
  * n > 4m, n > 3m) speak of every choice of messages.  These entries walk all of them
