@@ -58,13 +58,17 @@ EXPORTS = ["ba_version", "ba_device_count", "ba_ctx_create", "ba_ctx_destroy", "
            "ba_king3_coin_calls", "ba_king3_phases",
            "ba_rand_run_trials", "ba_rand_run_trials_device", "ba_rand_coin_calls",
            "ba_kenum_bits", "ba_kenum_slots", "ba_kenum_run", "ba_kenum_run_device",
-           "ba_smenum_bits", "ba_smenum_slots", "ba_smenum_run", "ba_smenum_run_device"]
+           "ba_smenum_bits", "ba_smenum_slots", "ba_smenum_run", "ba_smenum_run_device",
+           "ba_renum_bits", "ba_renum_slots", "ba_renum_run", "ba_renum_run_device"]
 KENUM_KING, KENUM_KING3 = 0, 1  # the protocol of run_kenum (docs/SEMANTICS.md §11)
 SMENUM_MESSAGES, SMENUM_COALITION = 0, 1  # the form of run_smenum (docs/SEMANTICS.md §12)
 SMENUM_ANY = 0xFFFFFFFF  # smenum_slots' sender in the coalition form's relay rounds: any traitor
 KENUM_MAX_N = 16  # k_kenum is built for n = 1..16
 ENUM_MAX_BITS = 48  # BA_ENUM_MAX_BITS (docs/SEMANTICS.md §8, §11, §12)
 NO_WITNESS = (1 << 64) - 1
+RENUM_MAX_PHASES, RENUM_NSTATS = 16, 20  # BA_RENUM_MAX_PHASES, BA_RENUM_NSTATS (docs/SEMANTICS.md §14)
+RENUM_TOSS = 2  # renum_slots' part of a toss bit
+RENUM_COMMON_COIN = 0xFFFFFFFF  # renum_slots' sender and recipient of the common coin's bit
 PROBE_BLOCKS = 2048  # BA_PROBE_BLOCKS
 
 
@@ -234,6 +238,13 @@ def load(path: str | None = None):
     lib.ba_smenum_slots.argtypes = [u32, u32, u32, u32, u32, vp, vp, vp, vp, u32]
     lib.ba_smenum_run.argtypes = lib.ba_kenum_run.argtypes
     lib.ba_smenum_run_device.argtypes = lib.ba_kenum_run_device.argtypes
+    lib.ba_renum_bits.argtypes = [u32, u32, u32, u32, u32]
+    lib.ba_renum_bits.restype = u32
+    lib.ba_renum_slots.argtypes = [u32, u32, u32, u32, u32, vp, vp, vp, vp, u32]
+    lib.ba_renum_run.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u32, u32, u64, vp, vp, vp,
+                                 ctypes.POINTER(Counters), ctypes.POINTER(u64), vp]
+    lib.ba_renum_run_device.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u32, u32, u64, vp, vp, vp,
+                                        vp, vp, vp, vp]
     if lib.ba_version() != ABI_VERSION:
         raise RuntimeError(f"libba_hip ABI {lib.ba_version()} != {ABI_VERSION}")
     if path is None:
@@ -288,6 +299,7 @@ class RunResult:
     witness: int | None = None  # run_enum: the smallest violating strategy, None when there is none
     settled: np.ndarray | None = None  # run_king / run_king3(want_settled=True): phase from which the loyal agree, 255 = never
     decided: np.ndarray | None = None  # run_rand(want_decided=True): phase by which every loyal general decided, 255 = not within R, 254 = unsafe
+    stats: dict | None = None  # run_renum: unsafe, undecided, unsafe_witness, undecided_witness, decided_in (renum_stats)
 
     def decision(self, t: int, r: int) -> int:
         """Decision code of lieutenant r (1..n-1) in trial t."""
@@ -559,6 +571,44 @@ class Engine:
         from the host, so a stream that is capturing a graph takes the call."""
         self._run_enum_device(self.lib.ba_smenum_run_device, (form,), params, faulty_mask, order, count,
                               d_decisions, d_outcome, d_counters, d_witness, stream)
+
+    def run_renum(self, coin, n, m, phases, faulty_mask, order, first=0, count=None, want_decisions=False,
+                  want_outcome=False, want_decided=False, lie_mode=LIE_PHILOX, faulty_mode=FAULTY_GIVEN,
+                  order_mode=ORDER_GIVEN, engine=ENGINE_AUTO) -> RunResult:
+        """Walk the strategies S in [first, first + count) of the RAND case (coin, n, m,
+        phases, faulty_mask, order): every traitor message and every coin outcome is a free
+        bit (docs/SEMANTICS.md §14; ba_renum_run); count=None: up to the end of the space,
+        2^renum_bits.  The result's `witness` is the smallest S whose final preferences
+        violate IC1 / IC2, `decided` the per-strategy byte of run_rand and `stats` the
+        dict of renum_stats (decode_rstrategy reads its two witnesses)."""
+        bits = renum_bits(coin, n, m, phases, faulty_mask)
+        if count is None:
+            count = max(0, (1 << bits) - first) if bits <= ENUM_MAX_BITS else 0  # above the cap: the call says so
+        dec = np.zeros(count, np.uint64) if want_decisions else None
+        out = np.zeros(count, np.uint8) if want_outcome else None
+        dcd = np.zeros(count, np.uint8) if want_decided else None
+        p = make_params(n, m, 0, lie_mode, faulty_mode, 0, order_mode, ATTACK, engine, first)
+        cnt, wit = Counters(), ctypes.c_uint64(NO_WITNESS)
+        stats = np.zeros(RENUM_NSTATS, np.uint64)
+        _check(self.lib, self.lib.ba_renum_run(self.handle, ctypes.byref(p), coin, phases,
+                                               faulty_mask & 0xFFFFFFFF, order, count, _ptr(dec), _ptr(out),
+                                               _ptr(dcd), ctypes.byref(cnt), ctypes.byref(wit), _ptr(stats)))
+        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])),
+                         witness=None if wit.value == NO_WITNESS else int(wit.value), decided=dcd,
+                         stats=renum_stats(stats))
+
+    def run_renum_device(self, params: Params, coin: int, phases: int, faulty_mask: int, order: int,
+                         count: int, d_decisions=0, d_outcome=0, d_decided=0, d_counters=0, d_witness=0,
+                         d_stats=0, stream=0):
+        """Enqueue strategies [params.first_trial, + count) on device pointers
+        (ba_renum_run_device); counters and the counts of d_stats (RENUM_NSTATS uint64)
+        accumulated; the witness, d_stats[2] and d_stats[3] (set to NO_WITNESS by the
+        caller) min-accumulated.  Fully asynchronous: nothing is copied from the host, so
+        a stream that is capturing a graph takes the call."""
+        _check(self.lib, self.lib.ba_renum_run_device(
+            self.handle, ctypes.byref(params), coin, phases, faulty_mask & 0xFFFFFFFF, order, count,
+            d_decisions or None, d_outcome or None, d_decided or None, d_counters or None,
+            d_witness or None, d_stats or None, stream or None))
 
     def stream(self) -> int:
         """The ctx's own HIP stream (ba_ctx_stream), as an int handle."""
@@ -1031,3 +1081,51 @@ def pack_coins(rows, n):
             if v:
                 tab[i, c >> 5] |= np.uint32(1 << (c & 31))
     return tab
+
+
+def renum_bits(coin: int, n: int, m: int, phases: int, faulty_mask: int) -> int:
+    """Free bits B of a RAND case's space of traitor messages and coin outcomes
+    (ba_renum_bits); 0xFFFFFFFF for a bad coin / n / m / phases."""
+    return int(load().ba_renum_bits(coin, n, m, phases, faulty_mask & 0xFFFFFFFF))
+
+
+def renum_slots(coin: int, n: int, m: int, phases: int, faulty_mask: int) -> list:
+    """[(q, sender, recipient, part)] of free bits 0..B-1 (ba_renum_slots): part is 0 for a
+    one-bit message, 0 / 1 for lo / hi of a proposal and RENUM_TOSS for a toss bit, whose
+    sender = recipient is the general (RAND_LOCAL) or RENUM_COMMON_COIN."""
+    lib = load()
+    b = renum_bits(coin, n, m, phases, faulty_mask)
+    cap = b if b != 0xFFFFFFFF else 0
+    arr = [np.zeros(max(cap, 1), np.uint32) for _ in range(4)]
+    got = lib.ba_renum_slots(coin, n, m, phases, faulty_mask & 0xFFFFFFFF, *(a.ctypes.data for a in arr), cap)
+    if got < 0:
+        raise BAError(got, lib.ba_last_error().decode())
+    return [tuple(int(a[i]) for a in arr) for i in range(got)]
+
+
+def renum_stats(words) -> dict:
+    """The BA_RENUM_NSTATS words of ba_renum_run as a dict: `unsafe` and `undecided`
+    counts, `unsafe_witness` and `undecided_witness` (the smallest such S, None for
+    none) and `decided_in`, a list indexed by phase (entry 0 is 0)."""
+    w = [int(x) & NO_WITNESS for x in words]
+    return {"unsafe": w[0], "undecided": w[1],
+            "unsafe_witness": None if w[2] == NO_WITNESS else w[2],
+            "undecided_witness": None if w[3] == NO_WITNESS else w[3],
+            "decided_in": [0] + w[4:4 + RENUM_MAX_PHASES]}
+
+
+def decode_rstrategy(coin: int, n: int, m: int, phases: int, faulty_mask: int, S: int) -> dict:
+    """{"messages": {(q, sender, recipient): 0 | 1 | None}, "coins": {(p, general or None):
+    bit}} of strategy S (docs/SEMANTICS.md §14): a message is 1 = attack / 0 = retreat, in
+    a propose round None is no proposal (lo = 0, whatever hi is); a coin is general g's
+    toss of phase p (RAND_LOCAL) or the common coin (p, None)."""
+    msgs, coins = {}, {}
+    for i, (q, j, r, part) in enumerate(renum_slots(coin, n, m, phases, faulty_mask)):
+        bit = (S >> i) & 1
+        if part == RENUM_TOSS:
+            coins[(q // 3, None if j == RENUM_COMMON_COIN else j)] = bit
+        elif part == 0:
+            msgs[(q, j, r)] = bit  # a proposal's lo for now
+        else:
+            msgs[(q, j, r)] = bit if msgs[(q, j, r)] else None
+    return {"messages": msgs, "coins": coins}

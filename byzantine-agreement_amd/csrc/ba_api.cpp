@@ -1085,6 +1085,7 @@ static int protocol_device_entry(ba_ctx* ctx, const ba_params* p, uint64_t batch
 // (the kernels take any batch in one launch; counters are zeroed once and
 // accumulate across the chunks on the device, trials keyed by their global index).
 constexpr uint64_t kHostChunk = 1ull << 24;
+constexpr uint32_t kHostTailMax = 1 + BA_RENUM_NSTATS;  // RENUM's witness and stats
 
 // One chunk queued on the ctx stream: the params with the chunk's first_trial, its
 // trials, the staged inputs and outputs (NULL where not given / not asked for), the
@@ -1107,6 +1108,11 @@ struct HostRun {
     const char* chunk_env = nullptr;   // tests: chunk a small batch (a multiple of 64)
     uint64_t chunk = kHostChunk;       // without the override
     uint64_t* tail = nullptr;          // the enumerations: the word after the counters, preset to all-ones
+    // RENUM: tail points at tail_words words, staged after the counters; bit w of
+    // tail_ones: word w is preset to all-ones (a min-accumulated witness), else to
+    // zero (a count)
+    uint32_t tail_words = 1;
+    uint32_t tail_ones = 1;
     std::function<int(hipStream_t)> before;  // the enumerations: once, ahead of the first chunk
     HostQueue queue;
 };
@@ -1121,7 +1127,9 @@ static int host_run(ba_ctx* ctx, const ba_params* p, uint64_t batch, const HostR
     const HostPlan h = host_plan(batch, r.chunk, getenv(r.chunk_env), r.decisions != nullptr,
                                  r.outcome != nullptr, r.extra != nullptr, r.extra_elem,
                                  r.extra_behind_dec);
-    const size_t cnt_bytes = (BA_NCOUNTERS + (r.tail ? 1 : 0)) * 8;
+    const uint32_t tail_words = r.tail ? r.tail_words : 0u;
+    if (tail_words > kHostTailMax) return fail(BA_EINVAL, "internal: %u tail words", tail_words);
+    const size_t cnt_bytes = (BA_NCOUNTERS + tail_words) * 8;
     int rc;
     if (need_f && (rc = ctx->io_faulty.grow(h.chunk * 4)) != BA_OK) return rc;
     if (need_o && (rc = ctx->io_order.grow(h.chunk)) != BA_OK) return rc;
@@ -1134,7 +1142,13 @@ static int host_run(ba_ctx* ctx, const ba_params* p, uint64_t batch, const HostR
     char* const extra_base = (char*)(r.extra_behind_dec ? ctx->io_dec.p : ctx->io_out.p);
     void* const d_extra = r.extra ? extra_base + h.extra_off : nullptr;
     HIP_TRY(hipMemsetAsync(d_cnt, 0, BA_NCOUNTERS * 8, st));
-    if (r.tail) HIP_TRY(hipMemsetAsync(d_cnt + BA_NCOUNTERS, 0xFF, 8, st));
+    for (uint32_t w = 0; w < tail_words;) {  // one memset per run of words preset alike
+        const uint32_t ones = (r.tail_ones >> w) & 1u;
+        uint32_t e = w + 1;
+        while (e < tail_words && ((r.tail_ones >> e) & 1u) == ones) ++e;
+        HIP_TRY(hipMemsetAsync(d_cnt + BA_NCOUNTERS + w, ones ? 0xFF : 0, (e - w) * 8, st));
+        w = e;
+    }
     if (r.before && (rc = r.before(st)) != BA_OK) return rc;
     ba_params q = *p;
     for (uint64_t t0 = 0; t0 < batch; t0 += h.chunk) {
@@ -1154,11 +1168,11 @@ static int host_run(ba_ctx* ctx, const ba_params* p, uint64_t batch, const HostR
             HIP_TRY(hipMemcpyAsync((char*)r.extra + t0 * r.extra_elem, d_extra, nt * r.extra_elem,
                                    hipMemcpyDeviceToHost, st));
     }
-    uint64_t h_cnt[BA_NCOUNTERS + 1];
+    uint64_t h_cnt[BA_NCOUNTERS + kHostTailMax];
     HIP_TRY(hipMemcpyAsync(h_cnt, d_cnt, cnt_bytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (r.counters) memcpy(r.counters->v, h_cnt, BA_NCOUNTERS * 8);
-    if (r.tail) *r.tail = h_cnt[BA_NCOUNTERS];
+    if (r.tail) memcpy(r.tail, h_cnt + BA_NCOUNTERS, tail_words * 8);
     return BA_OK;
 }
 
@@ -1897,6 +1911,158 @@ extern "C" int ba_smenum_run(ba_ctx* ctx, const ba_params* p, uint32_t form, uin
         ctx, p, batch, decisions, outcome, counters, witness, "BA_SMENUM_HOST_CHUNK",
         [&] { return validate_smenum(p, form, faulty_mask, order, batch, g); }, enum_no_prepare,
         [&](const RunArgs& a, uint64_t* w) { return launch_smenum(a, g, w); });
+}
+
+// ---------------------------------------------------------------------------
+// RAND against every traitor strategy and every coin outcome of one case
+// (docs/SEMANTICS.md §14; ba_renum.hip)
+// ---------------------------------------------------------------------------
+// The numbers of a case that its bit count and slot list are made of; ok = false:
+// bad coin, n, m or phases.
+struct RenumShape {
+    bool ok = false;
+    uint32_t F = 0, nf = 0, ell = 0;
+};
+
+static RenumShape renum_shape(uint32_t coin, uint32_t n, uint32_t m, uint32_t phases, uint32_t faulty_mask) {
+    RenumShape s;
+    if (coin > BA_RAND_COMMON || n < 1 || n > BA_MAX_GENERALS || m > kKing3MaxM || phases < 1 ||
+        phases > BA_RENUM_MAX_PHASES)
+        return s;
+    s.ok = true;
+    s.F = faulty_mask & general_mask(n);
+    s.nf = (uint32_t)__builtin_popcount(s.F);
+    s.ell = n - s.nf;
+    return s;
+}
+
+// B = [F_0] l + R (3 |F| l + (LOCAL ? l : 1))
+extern "C" uint32_t ba_renum_bits(uint32_t coin, uint32_t n, uint32_t m, uint32_t phases,
+                                  uint32_t faulty_mask) {
+    const RenumShape s = renum_shape(coin, n, m, phases, faulty_mask);
+    if (!s.ok) return 0xFFFFFFFFu;
+    const uint64_t toss = coin == BA_RAND_LOCAL ? s.ell : 1;
+    const uint64_t B = (uint64_t)(s.F & 1u) * s.ell + (uint64_t)phases * (3ull * s.nf * s.ell + toss);
+    return B > kEnumBitsSaturated ? kEnumBitsSaturated : (uint32_t)B;
+}
+
+extern "C" int ba_renum_slots(uint32_t coin, uint32_t n, uint32_t m, uint32_t phases,
+                              uint32_t faulty_mask, uint32_t* q, uint32_t* sender, uint32_t* recipient,
+                              uint32_t* part, uint32_t cap) {
+    const RenumShape s = renum_shape(coin, n, m, phases, faulty_mask);
+    if (!s.ok) return fail(BA_EINVAL, "coin=%u n=%u m=%u phases=%u", coin, n, m, phases);
+    const uint32_t B = ba_renum_bits(coin, n, m, phases, faulty_mask);
+    if (B > cap) return fail(BA_EINVAL, "cap=%u < %u free bits", cap, B);
+    if (B && (!q || !sender || !recipient || !part))
+        return fail(BA_EINVAL, "q, sender, recipient and part are required");
+    uint32_t bit = 0;
+    auto put = [&](uint32_t qq, uint32_t j, uint32_t i, uint32_t h) {
+        q[bit] = qq, sender[bit] = j, recipient[bit] = i, part[bit] = h;
+        ++bit;
+    };
+    // the free messages of round qq from sender j, in recipient order; parts bits each
+    auto round_of = [&](uint32_t qq, uint32_t j, uint32_t parts) {
+        if (!((s.F >> j) & 1u)) return;
+        for (uint32_t i = 0; i < n; ++i)
+            if (!((s.F >> i) & 1u))
+                for (uint32_t h = 0; h < parts; ++h) put(qq, j, i, h);
+    };
+    round_of(0, 0, 1);
+    for (uint32_t p = 1; p <= phases; ++p) {
+        for (uint32_t j = 0; j < n; ++j) round_of(3 * p - 2, j, 1);
+        for (uint32_t j = 0; j < n; ++j) round_of(3 * p - 1, j, 2);
+        if (coin == BA_RAND_COMMON) {
+            put(3 * p, 0xFFFFFFFFu, 0xFFFFFFFFu, 2);
+        } else {
+            for (uint32_t i = 0; i < n; ++i)
+                if (!((s.F >> i) & 1u)) put(3 * p, i, i, 2);
+        }
+    }
+    if (bit != B) return fail(BA_EINVAL, "internal: %u free bits listed, formula %u", bit, B);
+    return (int)B;
+}
+
+static int validate_renum(const ba_params* p, uint32_t coin, uint32_t phases, uint32_t faulty_mask,
+                          uint32_t order, uint64_t batch, RenumCase& g) {
+    if (coin > BA_RAND_COMMON) return fail(BA_EINVAL, "coin=%u", coin);
+    if (phases < 1 || phases > BA_RENUM_MAX_PHASES)
+        return fail(BA_EINVAL, "phases=%u outside [1,%d]", phases, BA_RENUM_MAX_PHASES);
+    char prefix[32];
+    snprintf(prefix, sizeof prefix, "coin=%u phases=%u ", coin, phases);
+    const uint32_t B = p ? ba_renum_bits(coin, p->n, p->m, phases, faulty_mask) : 0;
+    int rc = validate_enumeration(p, batch, "the RAND enumeration", kKing3MaxM, faulty_mask, order, B, prefix, [&] {
+        if (p->n > kRenumMaxN)
+            return fail(BA_ETOOBIG, "n=%u > %u: k_renum keeps three planes per general in registers", p->n,
+                        kRenumMaxN);
+        return (int)BA_OK;
+    });
+    if (rc != BA_OK) return rc;
+    const RenumShape s = renum_shape(coin, p->n, p->m, phases, faulty_mask);
+    g.coin = coin, g.m = p->m, g.phases = phases, g.fmask = s.F, g.order = order;
+    return BA_OK;
+}
+
+// launch(args, witness) of strategies from `first` on, whose per-trial decided bytes
+// start at `decided` (a launch range's later launches start further in)
+static auto renum_launch(const RenumCase& g, uint64_t first, uint8_t* decided, uint64_t* stats) {
+    return [&g, first, decided, stats](const RunArgs& a, uint64_t* w) {
+        return launch_renum(a, g, decided ? decided + (a.first_trial - first) : nullptr, w, stats);
+    };
+}
+
+extern "C" int ba_renum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t coin, uint32_t phases,
+                                   uint32_t faulty_mask, uint32_t order, uint64_t batch,
+                                   uint64_t* d_decisions, uint8_t* d_outcome, uint8_t* d_decided,
+                                   uint64_t* d_counters, uint64_t* d_witness, uint64_t* d_stats,
+                                   void* stream) {
+    RenumCase g{};
+    return enum_device_entry(
+        ctx, p, batch, d_decisions, d_outcome, d_counters, d_witness, stream, nullptr,
+        [&] { return validate_renum(p, coin, phases, faulty_mask, order, batch, g); }, enum_no_prepare,
+        [&](const RunArgs& a, uint64_t* w) {
+            return renum_launch(g, p->first_trial, d_decided, d_stats)(a, w);
+        });
+}
+
+// enum_host_entry's shape with two additions: the decided bytes ride behind the
+// outcome in io_out (HostRun::extra), and the words after the counters are the
+// witness and the BA_RENUM_NSTATS stats, accumulated on the device across the chunks.
+extern "C" int ba_renum_run(ba_ctx* ctx, const ba_params* p, uint32_t coin, uint32_t phases,
+                            uint32_t faulty_mask, uint32_t order, uint64_t batch, uint64_t* decisions,
+                            uint8_t* outcome, uint8_t* decided, ba_counters* counters, uint64_t* witness,
+                            uint64_t* stats) {
+    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
+    RenumCase g{};
+    int rc = validate_renum(p, coin, phases, faulty_mask, order, batch, g);
+    if (rc != BA_OK) return rc;
+    uint64_t tail[1 + BA_RENUM_NSTATS] = {};
+    tail[0] = tail[1 + 2] = tail[1 + 3] = UINT64_MAX;
+    auto give = [&] {
+        if (witness) *witness = tail[0];
+        if (stats) memcpy(stats, tail + 1, BA_RENUM_NSTATS * 8);
+    };
+    if (counters) memset(counters, 0, sizeof *counters);
+    give();
+    if (batch == 0) return BA_OK;
+    HostRun r;
+    r.decisions = decisions, r.outcome = outcome, r.counters = counters;
+    r.extra = decided, r.extra_elem = 1, r.extra_behind_dec = false;
+    r.tail = tail, r.tail_words = 1 + BA_RENUM_NSTATS;
+    r.tail_ones = 1u | (1u << (1 + 2)) | (1u << (1 + 3));
+    r.chunk_env = "BA_RENUM_HOST_CHUNK";
+    r.chunk = (decisions || outcome || decided) ? kHostChunk : batch;
+    r.before = [&](hipStream_t st) {
+        (void)ctx_mark(ctx, st);  // whatever follows: work of this ctx is queued on st
+        return (int)BA_OK;
+    };
+    r.queue = [&](const ba_params& q, uint64_t nt, const uint32_t*, const uint8_t*, uint64_t* d_dec,
+                  uint8_t* d_out, void* d_extra, uint64_t* d_cnt, hipStream_t st) {
+        return enum_launch_range(ctx, p, q.first_trial, nt, d_dec, d_out, d_cnt, d_cnt + BA_NCOUNTERS, st,
+                                 renum_launch(g, q.first_trial, (uint8_t*)d_extra, d_cnt + BA_NCOUNTERS + 1));
+    };
+    rc = host_run(ctx, p, batch, r);
+    if (rc == BA_OK) give();
+    return rc;
 }
 
 extern "C" int ba_split_votes_device(ba_ctx* ctx, const ba_params* p, uint64_t batch,

@@ -257,4 +257,21 @@ struct SmenumCase {
 };
 hipError_t launch_smenum(const RunArgs& a, const SmenumCase& g, uint64_t* witness);
 
+// RAND against every traitor strategy and coin outcome of one case (ba_renum.hip,
+// docs/SEMANTICS.md §14): trial t is strategy S = t.  n is a template parameter of
+// k_renum (the planes x, D, V of every general live in registers), instantiated for
+// 1..kRenumMaxN and both coins.  decided (a byte per strategy), witness and stats
+// (kRenumStats words in include/ba.h's order: counts added, words 2 and 3
+// min-accumulated) are optional.
+constexpr uint32_t kRenumMaxN = 16;
+constexpr uint32_t kRenumMaxPhases = 16;
+constexpr uint32_t kRenumStats = 4 + kRenumMaxPhases;
+struct RenumCase {
+    uint32_t coin;    // BA_RAND_LOCAL / BA_RAND_COMMON
+    uint32_t m, phases;
+    uint32_t fmask, order;  // fmask masked to n bits; order code 0..2
+};
+hipError_t launch_renum(const RunArgs& a, const RenumCase& g, uint8_t* decided, uint64_t* witness,
+                        uint64_t* stats);
+
 }  // namespace ba

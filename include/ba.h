@@ -626,6 +626,74 @@ int ba_smenum_run_device(struct ba_ctx* ctx, const ba_params* p, uint32_t form,
                          uint64_t* d_decisions, uint8_t* d_outcome, uint64_t* d_counters,
                          uint64_t* d_witness, void* stream);  /* accumulated, async */
 
+/* ---- RAND against every traitor strategy and every coin outcome of one case ------
+ * BA_KING_COIN and BA_KING_SPLIT do not see the coin; RAND's safety claim (no loyal
+ * general ever decides two values or leaves a decided value) speaks of every choice
+ * of messages and every fall of the coins.  These entries make both free bits and
+ * walk all of them for one case (coin, n, m, R = phases, faulty set, order)
+ * (docs/SEMANTICS.md §14; no ba.py analogue): each play of an adversary that sees
+ * the coins is one (messages, coins) pair, so the walk covers it too.  The rules are
+ * RAND's above, unchanged; every general, faulty ones included, keeps x, D and V and
+ * runs the rules honestly.  Messages are truth / dead / free as in the King
+ * enumeration: a dead report is retreat, a dead proposal is none; a free report or
+ * round-0 send is one bit (1 = attack); a free proposal is two consecutive bits
+ * (lo, hi), lo = 0 no proposal whatever hi is, lo = 1 proposes hi.  Tosses:
+ *   BA_RAND_LOCAL   one free bit per loyal general and phase, read only where that
+ *                   general has no v; a faulty general's own toss is dead (retreat);
+ *   BA_RAND_COMMON  one free bit per phase, taken by every general that tosses.
+ * With c = [0 in F], l = n - |F|, free bits ascend: round 0 (c l bits, by loyal
+ * rank), then per phase the reports (sender's rank among the traitors * l + the
+ * recipient's rank among the loyal), the proposals (twice that, lo then hi) and the
+ * tosses (LOCAL: l bits by loyal rank; COMMON: one):
+ *   B = c l + R (3 |F| l + (LOCAL ? l : 1))
+ * The two "no proposal" codes and a toss bit nobody reads play alike, so rates are
+ * rates over the coded space.  Trial t of a call is strategy S = t: a call covers S
+ * in [p->first_trial, p->first_trial + batch), first_trial a multiple of 64, ending
+ * at or below 2^B (else BA_EINVAL).  p supplies n, m and first_trial; seed and f are
+ * unused.  p->lie_mode must be BA_LIE_PHILOX (TABLE: BA_ENOTSUP), p->engine
+ * BA_ENGINE_AUTO, p->faulty_mode BA_FAULTY_GIVEN and p->order_mode BA_ORDER_GIVEN
+ * (else BA_EINVAL); coin > 1, phases outside 1..BA_RENUM_MAX_PHASES, order >
+ * BA_OTHER and m > 10 are BA_EINVAL.  B > BA_ENUM_MAX_BITS and n > 16 are
+ * BA_ETOOBIG: the kernel keeps three planes per general in registers and is built
+ * for n = 1..16.  One traitor alone costs at least 3 (n - 1) + 1 bits, over 48 from
+ * n = 17 on, so what the n cap loses beyond the bit cap is only the cases without
+ * any traitor (n in 17..32: B = R under COMMON, R n <= 48 under LOCAL).
+ * decisions / outcome / counters / witness: as in the King enumeration, in-bound is
+ * |F| <= m and n > 3m.  decided (optional, a byte per strategy): RAND's byte with its
+ * precedence, BA_RAND_UNSAFE, the first phase p at whose end every loyal general has
+ * D set (1 when nobody is loyal), BA_RAND_UNDECIDED.  stats (optional):
+ *   stats[0] unsafe strategies (decided == 254)      stats[1] undecided (255)
+ *   stats[2] smallest unsafe S    stats[3] smallest undecided S   (2^64-1: none)
+ *   stats[3 + p], p = 1..16: strategies with decided == p
+ *   stats[0] + stats[1] + sum_p stats[3 + p] == trials
+ * batch = 0: BA_OK, zero counters and counts, the three witnesses 2^64 - 1.  At most
+ * 2^40 strategies go into one launch.  Nothing is copied from host memory:
+ * ba_renum_run_device is fully asynchronous and may be captured in a graph. */
+#define BA_RENUM_MAX_PHASES 16
+#define BA_RENUM_NSTATS 20
+/* B; host only.  0xFFFFFFFF for coin > 1, n outside 1..32, m > 10 or phases outside
+ * 1..16; saturates at 0xFFFFFFFE.  Not limited to n <= 16. */
+uint32_t ba_renum_bits(uint32_t coin, uint32_t n, uint32_t m, uint32_t phases, uint32_t faulty_mask);
+/* bit i -> the message (q[i], sender[i] -> recipient[i]) and part[i]: 0 for a one-bit
+ * message, 0 / 1 for lo / hi of a proposal, 2 for a toss bit (q = 3p; sender =
+ * recipient = the general under LOCAL, both 0xFFFFFFFF under COMMON); host only.
+ * Returns B, or BA_EINVAL (bad arguments as above, cap < B, a missing array). */
+int ba_renum_slots(uint32_t coin, uint32_t n, uint32_t m, uint32_t phases, uint32_t faulty_mask,
+                   uint32_t* q, uint32_t* sender, uint32_t* recipient, uint32_t* part, uint32_t cap);
+int ba_renum_run(struct ba_ctx* ctx, const ba_params* p, uint32_t coin, uint32_t phases,
+                 uint32_t faulty_mask, uint32_t order, uint64_t batch, uint64_t* decisions,
+                 uint8_t* outcome, uint8_t* decided, ba_counters* counters, uint64_t* witness,
+                 uint64_t stats[BA_RENUM_NSTATS]);  /* counters, witness and stats overwritten */
+/* The same walk on device buffers, enqueued on `stream` in the ctx's call order
+ * (NULL = HIP's null stream).  d_counters and the counts of d_stats are accumulated
+ * into; d_witness, d_stats[2] and d_stats[3] (d_witness and d_stats optional) are
+ * min-accumulated: the caller sets them to 2^64 - 1 first. */
+int ba_renum_run_device(struct ba_ctx* ctx, const ba_params* p, uint32_t coin, uint32_t phases,
+                        uint32_t faulty_mask, uint32_t order, uint64_t batch,
+                        uint64_t* d_decisions, uint8_t* d_outcome, uint8_t* d_decided,
+                        uint64_t* d_counters, uint64_t* d_witness, uint64_t* d_stats,
+                        void* stream);  /* accumulated, async */
+
 /* ---- one huge instance split by first-hop subtree --------
  * The subtree of first-hop lieutenant j (relay paths starting 0 -> j) needs
  * only L_0[j]; its relay levels and inner majorities are independent of the
