@@ -485,20 +485,26 @@ class Engine:
             d_counters or None, stream or None))
 
     def _run_enum(self, fn, bits, lead, n, m, faulty_mask, order, first, count, want_decisions, want_outcome,
-                  lie_mode, faulty_mode, order_mode, engine) -> RunResult:
+                  lie_mode, faulty_mode, order_mode, engine, want_decided=None) -> RunResult:
         """The host entry `fn` of one enumeration over strategies [first, first + count).
         bits: the case's free bits, for count=None; lead: the entry's arguments between
-        params and faulty_mask (proto / form), () when it has none."""
+        params and faulty_mask (proto / form), () when it has none.  want_decided other
+        than None: the entry is RENUM's, with a decided plane after the outcome and the
+        stats words after the witness."""
         if count is None:
             count = max(0, (1 << bits) - first) if bits <= ENUM_MAX_BITS else 0  # above the cap: the call says so
         dec = np.zeros(count, np.uint64) if want_decisions else None
         out = np.zeros(count, np.uint8) if want_outcome else None
+        dcd = np.zeros(count, np.uint8) if want_decided else None
+        stats = None if want_decided is None else np.zeros(RENUM_NSTATS, np.uint64)
         p = make_params(n, m, 0, lie_mode, faulty_mode, 0, order_mode, ATTACK, engine, first)
         cnt, wit = Counters(), ctypes.c_uint64(NO_WITNESS)
+        plane, words = ((), ()) if stats is None else ((_ptr(dcd),), (_ptr(stats),))
         _check(self.lib, fn(self.handle, ctypes.byref(p), *lead, faulty_mask & 0xFFFFFFFF, order, count,
-                            _ptr(dec), _ptr(out), ctypes.byref(cnt), ctypes.byref(wit)))
+                            _ptr(dec), _ptr(out), *plane, ctypes.byref(cnt), ctypes.byref(wit), *words))
         return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])),
-                         witness=None if wit.value == NO_WITNESS else int(wit.value))
+                         witness=None if wit.value == NO_WITNESS else int(wit.value), decided=dcd,
+                         stats=None if stats is None else renum_stats(stats))
 
     def _run_enum_device(self, fn, lead, params, faulty_mask, order, count, d_decisions, d_outcome,
                          d_counters, d_witness, stream):
@@ -581,21 +587,9 @@ class Engine:
         2^renum_bits.  The result's `witness` is the smallest S whose final preferences
         violate IC1 / IC2, `decided` the per-strategy byte of run_rand and `stats` the
         dict of renum_stats (decode_rstrategy reads its two witnesses)."""
-        bits = renum_bits(coin, n, m, phases, faulty_mask)
-        if count is None:
-            count = max(0, (1 << bits) - first) if bits <= ENUM_MAX_BITS else 0  # above the cap: the call says so
-        dec = np.zeros(count, np.uint64) if want_decisions else None
-        out = np.zeros(count, np.uint8) if want_outcome else None
-        dcd = np.zeros(count, np.uint8) if want_decided else None
-        p = make_params(n, m, 0, lie_mode, faulty_mode, 0, order_mode, ATTACK, engine, first)
-        cnt, wit = Counters(), ctypes.c_uint64(NO_WITNESS)
-        stats = np.zeros(RENUM_NSTATS, np.uint64)
-        _check(self.lib, self.lib.ba_renum_run(self.handle, ctypes.byref(p), coin, phases,
-                                               faulty_mask & 0xFFFFFFFF, order, count, _ptr(dec), _ptr(out),
-                                               _ptr(dcd), ctypes.byref(cnt), ctypes.byref(wit), _ptr(stats)))
-        return RunResult(dec, out, dict(zip(COUNTER_NAMES, [int(x) for x in cnt.v])),
-                         witness=None if wit.value == NO_WITNESS else int(wit.value), decided=dcd,
-                         stats=renum_stats(stats))
+        return self._run_enum(self.lib.ba_renum_run, renum_bits(coin, n, m, phases, faulty_mask), (coin, phases),
+                              n, m, faulty_mask, order, first, count, want_decisions, want_outcome, lie_mode,
+                              faulty_mode, order_mode, engine, want_decided=bool(want_decided))
 
     def run_renum_device(self, params: Params, coin: int, phases: int, faulty_mask: int, order: int,
                          count: int, d_decisions=0, d_outcome=0, d_decided=0, d_counters=0, d_witness=0,
@@ -967,31 +961,46 @@ def kenum_bits(proto: int, n: int, m: int, faulty_mask: int) -> int:
     return int(load().ba_kenum_bits(proto, n, m, faulty_mask & 0xFFFFFFFF))
 
 
-def kenum_slots(proto: int, n: int, m: int, faulty_mask: int) -> list:
-    """[(q, sender, recipient, part)] of free bits 0..B-1 (ba_kenum_slots): part is 0 for a
-    one-bit message, 0 / 1 for lo / hi of a KING3 proposal."""
+def _slots(fn, bits: int, *case) -> list:
+    """The four-number rows of free bits 0..B-1 from the slot lister `fn` of a case
+    with `bits` free bits; case: the lister's arguments ahead of its arrays."""
     lib = load()
-    b = kenum_bits(proto, n, m, faulty_mask)
-    cap = b if b != 0xFFFFFFFF else 0
+    cap = bits if bits != 0xFFFFFFFF else 0
     arr = [np.zeros(max(cap, 1), np.uint32) for _ in range(4)]
-    got = lib.ba_kenum_slots(proto, n, m, faulty_mask & 0xFFFFFFFF, *(a.ctypes.data for a in arr), cap)
+    got = fn(*case, *(a.ctypes.data for a in arr), cap)
     if got < 0:
         raise BAError(got, lib.ba_last_error().decode())
     return [tuple(int(a[i]) for a in arr) for i in range(got)]
+
+
+def _decode_messages(slots, S: int, toss=None) -> tuple:
+    """({(q, sender, recipient): value}, [(q, sender, bit)] of the toss bits) of strategy
+    S over `slots`: a one-bit message is its bit; a proposal (parts 0 / 1 = lo / hi) is
+    None when withheld (lo = 0, whatever hi is), else hi."""
+    msgs, tosses = {}, []
+    for i, (q, j, r, part) in enumerate(slots):
+        bit = (S >> i) & 1
+        if part == toss:
+            tosses.append((q, j, bit))
+        elif part == 0:
+            msgs[(q, j, r)] = bit  # a proposal's lo for now
+        else:
+            msgs[(q, j, r)] = bit if msgs[(q, j, r)] else None
+    return msgs, tosses
+
+
+def kenum_slots(proto: int, n: int, m: int, faulty_mask: int) -> list:
+    """[(q, sender, recipient, part)] of free bits 0..B-1 (ba_kenum_slots): part is 0 for a
+    one-bit message, 0 / 1 for lo / hi of a KING3 proposal."""
+    return _slots(load().ba_kenum_slots, kenum_bits(proto, n, m, faulty_mask), proto, n, m,
+                  faulty_mask & 0xFFFFFFFF)
 
 
 def decode_kstrategy(proto: int, n: int, m: int, faulty_mask: int, S: int) -> dict:
     """{(q, sender, recipient): value} of the free messages under strategy S
     (docs/SEMANTICS.md §11): 1 = attack / 0 = retreat; in KING3's propose round None is
     no proposal (lo = 0, whatever hi is), else the value proposed."""
-    out = {}
-    for i, (q, j, r, part) in enumerate(kenum_slots(proto, n, m, faulty_mask)):
-        bit = (S >> i) & 1
-        if part == 0:
-            out[(q, j, r)] = bit  # a proposal's lo for now
-        else:
-            out[(q, j, r)] = bit if out[(q, j, r)] else None
-    return out
+    return _decode_messages(kenum_slots(proto, n, m, faulty_mask), S)[0]
 
 
 def encode_kstrategy(proto: int, n: int, m: int, faulty_mask: int, values) -> int:
@@ -1034,15 +1043,8 @@ def smenum_slots(form: int, n: int, m: int, faulty_mask: int, order: int) -> lis
     of round k that the bit sends when set; sender is SMENUM_ANY ("any traitor") in the
     coalition form's relay rounds.  `order` decides the values only when the commander
     is loyal."""
-    lib = load()
-    b = smenum_bits(form, n, m, faulty_mask)
-    cap = b if b != 0xFFFFFFFF else 0
-    arr = [np.zeros(max(cap, 1), np.uint32) for _ in range(4)]
-    got = lib.ba_smenum_slots(form, n, m, faulty_mask & 0xFFFFFFFF, order,
-                              *(a.ctypes.data for a in arr), cap)
-    if got < 0:
-        raise BAError(got, lib.ba_last_error().decode())
-    return [tuple(int(a[i]) for a in arr) for i in range(got)]
+    return _slots(load().ba_smenum_slots, smenum_bits(form, n, m, faulty_mask), form, n, m,
+                  faulty_mask & 0xFFFFFFFF, order)
 
 
 def decode_smstrategy(form: int, n: int, m: int, faulty_mask: int, order: int, S: int) -> list:
@@ -1093,14 +1095,8 @@ def renum_slots(coin: int, n: int, m: int, phases: int, faulty_mask: int) -> lis
     """[(q, sender, recipient, part)] of free bits 0..B-1 (ba_renum_slots): part is 0 for a
     one-bit message, 0 / 1 for lo / hi of a proposal and RENUM_TOSS for a toss bit, whose
     sender = recipient is the general (RAND_LOCAL) or RENUM_COMMON_COIN."""
-    lib = load()
-    b = renum_bits(coin, n, m, phases, faulty_mask)
-    cap = b if b != 0xFFFFFFFF else 0
-    arr = [np.zeros(max(cap, 1), np.uint32) for _ in range(4)]
-    got = lib.ba_renum_slots(coin, n, m, phases, faulty_mask & 0xFFFFFFFF, *(a.ctypes.data for a in arr), cap)
-    if got < 0:
-        raise BAError(got, lib.ba_last_error().decode())
-    return [tuple(int(a[i]) for a in arr) for i in range(got)]
+    return _slots(load().ba_renum_slots, renum_bits(coin, n, m, phases, faulty_mask), coin, n, m, phases,
+                  faulty_mask & 0xFFFFFFFF)
 
 
 def renum_stats(words) -> dict:
@@ -1119,13 +1115,6 @@ def decode_rstrategy(coin: int, n: int, m: int, phases: int, faulty_mask: int, S
     bit}} of strategy S (docs/SEMANTICS.md §14): a message is 1 = attack / 0 = retreat, in
     a propose round None is no proposal (lo = 0, whatever hi is); a coin is general g's
     toss of phase p (RAND_LOCAL) or the common coin (p, None)."""
-    msgs, coins = {}, {}
-    for i, (q, j, r, part) in enumerate(renum_slots(coin, n, m, phases, faulty_mask)):
-        bit = (S >> i) & 1
-        if part == RENUM_TOSS:
-            coins[(q // 3, None if j == RENUM_COMMON_COIN else j)] = bit
-        elif part == 0:
-            msgs[(q, j, r)] = bit  # a proposal's lo for now
-        else:
-            msgs[(q, j, r)] = bit if msgs[(q, j, r)] else None
-    return {"messages": msgs, "coins": coins}
+    msgs, tosses = _decode_messages(renum_slots(coin, n, m, phases, faulty_mask), S, toss=RENUM_TOSS)
+    return {"messages": msgs,
+            "coins": {(q // 3, None if j == RENUM_COMMON_COIN else j): bit for q, j, bit in tosses}}

@@ -1444,10 +1444,11 @@ extern "C" int ba_rand_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t poli
 }
 
 // ---------------------------------------------------------------------------
-// The exhaustive enumerations ENUM, KENUM and SMENUM (docs/SEMANTICS.md §8, §11,
-// §12): trial t of a call is strategy t of one case.  What they share: the
-// validation tail, the launch range, the device entry and the host entry.  An
-// enumeration is its bit count and slot list, its case set-up and its launch_*.
+// The exhaustive enumerations ENUM, KENUM, SMENUM and RENUM (docs/SEMANTICS.md §8,
+// §11, §12, §14): trial t of a call is strategy t of one case.  What they share: the
+// validation tail, the launch range, the device entry, the host entry, the case's
+// shape and the slot list's core.  An enumeration is its bit count and slot
+// schedule, its case set-up and its launch_*.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kEnumBitsSaturated = 0xFFFFFFFEu;
 
@@ -1455,13 +1456,25 @@ constexpr uint32_t kEnumBitsSaturated = 0xFFFFFFFEu;
 // (at most 31 decisions per strategy) stay below 2^48.
 constexpr uint64_t kEnumLaunchMax = 1ull << 40;
 
+// How an enumeration's messages name its case: `prefix`, the leading arguments ahead
+// of n in the cap's message (a format of at most two numbers), and, for a kernel that
+// keeps planes per general in registers, the n it takes and what it `keeps`.
+struct EnumLead {
+    char prefix[32];
+    uint32_t max_n = BA_MAX_GENERALS;
+    const char* keeps = nullptr;
+    EnumLead(const char* fmt = "", uint32_t a = 0, uint32_t b = 0) { snprintf(prefix, sizeof prefix, fmt, a, b); }
+};
+
+static int enum_no_pre() { return BA_OK; }
+
 // The checks of an enumeration after its own leading argument, in the order that
-// decides which error wins: validate_protocol, one given faulty set and order,
-// pre() (what the protocol checks ahead of the bit cap), the cap on the case's B free
-// bits, the range inside 2^B.  `prefix` names the case ahead of n in the cap's message.
+// decides which error wins: validate_protocol, one given faulty set and order, the n
+// of a register-plane kernel, pre() (what else the protocol checks ahead of the bit
+// cap), the cap on the case's B free bits, the range inside 2^B.
 template <typename Pre>
 static int validate_enumeration(const ba_params* p, uint64_t batch, const char* what, uint32_t max_m,
-                                uint32_t faulty_mask, uint32_t order, uint32_t B, const char* prefix,
+                                uint32_t faulty_mask, uint32_t order, uint32_t B, const EnumLead& lead,
                                 Pre&& pre) {
     int rc = validate_protocol(p, batch, true, true, what, max_m);
     if (rc != BA_OK) return rc;
@@ -1469,9 +1482,11 @@ static int validate_enumeration(const ba_params* p, uint64_t batch, const char* 
         return fail(BA_EINVAL, "faulty_mode=%u order_mode=%u: one given faulty set and order per call "
                     "(BA_FAULTY_GIVEN, BA_ORDER_GIVEN)", p->faulty_mode, p->order_mode);
     if (order > BA_OTHER) return fail(BA_EINVAL, "order=%u", order);
+    if (p->n > lead.max_n)
+        return fail(BA_ETOOBIG, "n=%u > %u: %s per general in registers", p->n, lead.max_n, lead.keeps);
     if ((rc = pre()) != BA_OK) return rc;
     if (B > BA_ENUM_MAX_BITS)
-        return fail(BA_ETOOBIG, "%sn=%u m=%u faulty_mask=0x%x: %u free bits > %d", prefix, p->n, p->m,
+        return fail(BA_ETOOBIG, "%sn=%u m=%u faulty_mask=0x%x: %u free bits > %d", lead.prefix, p->n, p->m,
                     faulty_mask, B, BA_ENUM_MAX_BITS);
     const uint64_t space = 1ull << B;  // B <= 48
     if (p->first_trial > space || batch > space - p->first_trial)
@@ -1520,41 +1535,114 @@ static int enum_device_entry(ba_ctx* ctx, const ba_params* p, uint64_t batch, ui
     });
 }
 
+// What a host entry gives back beside decisions, outcome, counters and the witness
+// (RENUM): one more per-strategy output, staged behind the outcome in io_out
+// (HostRun::extra), and `count` words after the witness; bit w of `ones`: word w is
+// min-accumulated and starts as all-ones, else it is a count and starts as zero.
+// The launch of a chunk finds its first strategy and its staged plane here, and the
+// words behind its witness argument.
+struct EnumHostMore {
+    void* plane = nullptr;
+    size_t elem = 0;
+    uint64_t* words = nullptr;
+    uint32_t count = 0, ones = 0;
+    uint64_t first = 0;
+    void* d_plane = nullptr;
+};
+
 // An enumeration's host entry: host_run with no inputs to copy; counters only: one
 // chunk, chunks of kHostChunk strategies when a per-trial output is asked for (the
-// witness min-accumulates across them on the device, in the word after the
+// witness and the words of `more` accumulate across them on the device, after the
 // counters).  The case is validated and prepared once for all the chunks.
 template <typename Check, typename Prepare, typename Launch>
 static int enum_host_entry(ba_ctx* ctx, const ba_params* p, uint64_t batch, uint64_t* decisions,
                            uint8_t* outcome, ba_counters* counters, uint64_t* witness,
-                           const char* chunk_env, Check&& check, Prepare&& prepare, Launch&& launch) {
+                           const char* chunk_env, Check&& check, Prepare&& prepare, Launch&& launch,
+                           EnumHostMore* more_if = nullptr) {
+    EnumHostMore none;
+    EnumHostMore& more = more_if ? *more_if : none;
     if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
     int rc = check();
     if (rc != BA_OK) return rc;
+    uint64_t tail[kHostTailMax] = {};
+    const uint32_t tail_ones = 1u | (more.ones << 1);
+    for (uint32_t w = 0; w < kHostTailMax; ++w)
+        if ((tail_ones >> w) & 1u) tail[w] = UINT64_MAX;
+    auto give = [&] {
+        if (witness) *witness = tail[0];
+        if (more.words) memcpy(more.words, tail + 1, more.count * 8);
+    };
     if (counters) memset(counters, 0, sizeof *counters);
-    if (witness) *witness = UINT64_MAX;
+    give();
     if (batch == 0) return BA_OK;
-    uint64_t wit = UINT64_MAX;
     HostRun r;
-    r.decisions = decisions, r.outcome = outcome, r.counters = counters, r.tail = &wit;
+    r.decisions = decisions, r.outcome = outcome, r.counters = counters;
+    r.extra = more.plane, r.extra_elem = more.elem, r.extra_behind_dec = false;
+    r.tail = tail, r.tail_words = 1 + more.count, r.tail_ones = tail_ones;
     r.chunk_env = chunk_env;
-    r.chunk = (decisions || outcome) ? kHostChunk : batch;
+    r.chunk = (decisions || outcome || more.plane) ? kHostChunk : batch;
     r.before = [&](hipStream_t st) {
         const int rc = prepare(st);
         (void)ctx_mark(ctx, st);  // whatever follows: work of this ctx is queued on st
         return rc;
     };
     r.queue = [&](const ba_params& q, uint64_t nt, const uint32_t*, const uint8_t*, uint64_t* d_dec,
-                  uint8_t* d_out, void*, uint64_t* d_cnt, hipStream_t st) {
+                  uint8_t* d_out, void* d_plane, uint64_t* d_cnt, hipStream_t st) {
+        more.first = q.first_trial, more.d_plane = d_plane;
         return enum_launch_range(ctx, p, q.first_trial, nt, d_dec, d_out, d_cnt, d_cnt + BA_NCOUNTERS, st,
                                  launch);
     };
     rc = host_run(ctx, p, batch, r);
-    if (rc == BA_OK && witness) *witness = wit;
+    if (rc == BA_OK) give();
     return rc;
 }
 
 static int enum_no_prepare(hipStream_t) { return BA_OK; }
+
+// What every case's bit count and slot list start from: the faulty set inside n, |F|
+// and the loyal generals.
+struct CaseShape {
+    uint32_t F = 0, nf = 0, ell = 0;
+};
+
+static CaseShape case_shape(uint32_t n, uint32_t faulty_mask) {
+    CaseShape s;
+    s.F = faulty_mask & general_mask(n);
+    s.nf = (uint32_t)__builtin_popcount(s.F);
+    s.ell = n - s.nf;
+    return s;
+}
+
+// The slot list of a case with B free bits, four numbers a bit: the checks of the
+// caller's arrays, the cursor `bit`, and the rounds whose free messages are the
+// traitors' to the loyal generals (KENUM, RENUM).
+struct SlotList {
+    uint32_t n, F, B;
+    uint32_t* col[4];
+    uint32_t bit = 0;
+
+    // after the case's own checks; `names` are the arrays' in the message
+    int check(uint32_t cap, const char* names) const {
+        if (B > cap) return fail(BA_EINVAL, "cap=%u < %u free bits", cap, B);
+        if (B && (!col[0] || !col[1] || !col[2] || !col[3])) return fail(BA_EINVAL, "%s are required", names);
+        return BA_OK;
+    }
+    void put(uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3) {
+        col[0][bit] = v0, col[1][bit] = v1, col[2][bit] = v2, col[3][bit] = v3;
+        ++bit;
+    }
+    // the free messages of round q from sender j, in recipient order; parts bits each
+    void round_of(uint32_t q, uint32_t j, uint32_t parts) {
+        if (!((F >> j) & 1u)) return;
+        for (uint32_t i = 0; i < n; ++i)
+            if (!((F >> i) & 1u))
+                for (uint32_t h = 0; h < parts; ++h) put(q, j, i, h);
+    }
+    int close() const {
+        if (bit != B) return fail(BA_EINVAL, "internal: %u free bits listed, formula %u", bit, B);
+        return (int)B;
+    }
+};
 
 // ---------------------------------------------------------------------------
 // OM(m) against every traitor strategy of one case (docs/SEMANTICS.md §8; ba_enum.hip)
@@ -1711,8 +1799,8 @@ extern "C" int ba_enum_run(ba_ctx* ctx, const ba_params* p, uint32_t faulty_mask
 // ---------------------------------------------------------------------------
 // The numbers of a case that its bit count and slot list are made of; P = 0: bad
 // proto, n or m.
-struct KenumShape {
-    uint32_t P = 0, F = 0, nf = 0, ell = 0, fK = 0;
+struct KenumShape : CaseShape {
+    uint32_t P = 0, fK = 0;
 };
 
 static KenumShape kenum_shape(uint32_t proto, uint32_t n, uint32_t m, uint32_t faulty_mask) {
@@ -1720,9 +1808,7 @@ static KenumShape kenum_shape(uint32_t proto, uint32_t n, uint32_t m, uint32_t f
     if (proto > BA_KENUM_KING3) return s;
     s.P = proto == BA_KENUM_KING ? ba_king_phases(n, m) : ba_king3_phases(n, m);
     if (s.P == 0) return s;
-    s.F = faulty_mask & general_mask(n);
-    s.nf = (uint32_t)__builtin_popcount(s.F);
-    s.ell = n - s.nf;
+    static_cast<CaseShape&>(s) = case_shape(n, faulty_mask);
     s.fK = (uint32_t)__builtin_popcount(s.F & general_mask(s.P));  // the kings are generals 0..P-1
     return s;
 }
@@ -1741,46 +1827,28 @@ extern "C" int ba_kenum_slots(uint32_t proto, uint32_t n, uint32_t m, uint32_t f
                               uint32_t cap) {
     const KenumShape s = kenum_shape(proto, n, m, faulty_mask);
     if (s.P == 0) return fail(BA_EINVAL, "proto=%u n=%u m=%u", proto, n, m);
-    const uint32_t B = ba_kenum_bits(proto, n, m, faulty_mask);
-    if (B > cap) return fail(BA_EINVAL, "cap=%u < %u free bits", cap, B);
-    if (B && (!q || !sender || !recipient || !part))
-        return fail(BA_EINVAL, "q, sender, recipient and part are required");
-    uint32_t bit = 0;
-    // the free messages of round qq from sender j, in recipient order; parts bits each
-    auto round_of = [&](uint32_t qq, uint32_t j, uint32_t parts) {
-        if (!((s.F >> j) & 1u)) return;
-        for (uint32_t i = 0; i < n; ++i) {
-            if ((s.F >> i) & 1u) continue;
-            for (uint32_t h = 0; h < parts; ++h, ++bit)
-                q[bit] = qq, sender[bit] = j, recipient[bit] = i, part[bit] = h;
-        }
-    };
+    SlotList sl{n, s.F, ba_kenum_bits(proto, n, m, faulty_mask), {q, sender, recipient, part}};
+    if (const int rc = sl.check(cap, "q, sender, recipient and part")) return rc;
     const uint32_t per = proto == BA_KENUM_KING ? 2 : 3;  // rounds of a phase
-    round_of(0, 0, 1);
+    sl.round_of(0, 0, 1);
     for (uint32_t p = 1; p <= s.P; ++p) {
-        for (uint32_t j = 0; j < n; ++j) round_of(per * p - (per - 1), j, 1);
+        for (uint32_t j = 0; j < n; ++j) sl.round_of(per * p - (per - 1), j, 1);
         if (proto == BA_KENUM_KING3)
-            for (uint32_t j = 0; j < n; ++j) round_of(3 * p - 1, j, 2);
-        round_of(per * p, p - 1, 1);
+            for (uint32_t j = 0; j < n; ++j) sl.round_of(3 * p - 1, j, 2);
+        sl.round_of(per * p, p - 1, 1);
     }
-    if (bit != B) return fail(BA_EINVAL, "internal: %u free bits listed, formula %u", bit, B);
-    return (int)B;
+    return sl.close();
 }
 
 static int validate_kenum(const ba_params* p, uint32_t proto, uint32_t faulty_mask, uint32_t order,
                           uint64_t batch, KenumCase& g) {
     if (proto > BA_KENUM_KING3) return fail(BA_EINVAL, "proto=%u", proto);
-    char prefix[24];
-    snprintf(prefix, sizeof prefix, "proto=%u ", proto);
+    EnumLead lead("proto=%u ", proto);
+    lead.max_n = kKenumMaxN, lead.keeps = "k_kenum keeps one plane";
     const uint32_t B = p ? ba_kenum_bits(proto, p->n, p->m, faulty_mask) : 0;
-    int rc = validate_enumeration(
-        p, batch, "the King enumeration", proto == BA_KENUM_KING ? (uint32_t)BA_MAX_DEPTH : kKing3MaxM,
-        faulty_mask, order, B, prefix, [&] {
-            if (p->n > kKenumMaxN)
-                return fail(BA_ETOOBIG, "n=%u > %u: k_kenum keeps one plane per general in registers", p->n,
-                            kKenumMaxN);
-            return (int)BA_OK;
-        });
+    int rc = validate_enumeration(p, batch, "the King enumeration",
+                                  proto == BA_KENUM_KING ? (uint32_t)BA_MAX_DEPTH : kKing3MaxM, faulty_mask,
+                                  order, B, lead, enum_no_pre);
     if (rc != BA_OK) return rc;
     const KenumShape s = kenum_shape(proto, p->n, p->m, faulty_mask);
     g.proto = proto, g.m = p->m, g.phases = s.P, g.fmask = s.F, g.order = order;
@@ -1823,10 +1891,11 @@ static SmenumShape smenum_shape(uint32_t form, uint32_t n, uint32_t m, uint32_t 
     SmenumShape s;
     if (form > BA_SMENUM_COALITION || n < 1 || n > BA_MAX_GENERALS || m > BA_MAX_DEPTH) return s;
     s.ok = true;
-    s.F = faulty_mask & general_mask(n);
+    const CaseShape cs = case_shape(n, faulty_mask);
+    s.F = cs.F;
     s.c = s.F & 1u;
-    s.fL = (uint32_t)__builtin_popcount(s.F >> 1);
-    s.ell = n - 1 - s.fL;
+    s.fL = cs.nf - s.c;
+    s.ell = n - 1 - s.fL;  // the loyal lieutenants
     s.me = effective_depth(n, m);
     s.K = s.me < s.fL ? s.me : s.fL;
     return s;
@@ -1847,22 +1916,16 @@ extern "C" int ba_smenum_slots(uint32_t form, uint32_t n, uint32_t m, uint32_t f
     const SmenumShape s = smenum_shape(form, n, m, faulty_mask);
     if (!s.ok) return fail(BA_EINVAL, "form=%u n=%u m=%u", form, n, m);
     if (order > BA_OTHER) return fail(BA_EINVAL, "order=%u", order);
-    const uint32_t B = ba_smenum_bits(form, n, m, faulty_mask);
-    if (B > cap) return fail(BA_EINVAL, "cap=%u < %u free bits", cap, B);
-    if (B && (!k || !sender || !recipient || !value))
-        return fail(BA_EINVAL, "k, sender, recipient and value are required");
+    SlotList sl{n, s.F, ba_smenum_bits(form, n, m, faulty_mask), {k, sender, recipient, value}};
+    if (const int rc = sl.check(cap, "k, sender, recipient and value")) return rc;
     const uint32_t ob = order == BA_ATTACK ? 1 : 0;
-    uint32_t bit = 0;
     // the free messages of round kk from sender j (general index, or "any traitor"),
     // in recipient order: both values under a faulty commander, else the order's
     auto round_of = [&](uint32_t kk, uint32_t j) {
         for (uint32_t i = 1; i < n; ++i) {
             if ((s.F >> i) & 1u) continue;
-            for (uint32_t v = 0; v < 2; ++v) {
-                if (!s.c && v != ob) continue;
-                k[bit] = kk, sender[bit] = j, recipient[bit] = i, value[bit] = v;
-                ++bit;
-            }
+            for (uint32_t v = 0; v < 2; ++v)
+                if (s.c || v == ob) sl.put(kk, j, i, v);
         }
     };
     if (s.c) round_of(0, 0);
@@ -1874,18 +1937,15 @@ extern "C" int ba_smenum_slots(uint32_t form, uint32_t n, uint32_t m, uint32_t f
         for (uint32_t j = 1; j < n; ++j)
             if ((s.F >> j) & 1u) round_of(kk, j);
     }
-    if (bit != B) return fail(BA_EINVAL, "internal: %u free bits listed, formula %u", bit, B);
-    return (int)B;
+    return sl.close();
 }
 
 static int validate_smenum(const ba_params* p, uint32_t form, uint32_t faulty_mask, uint32_t order,
                            uint64_t batch, SmenumCase& g) {
     if (form > BA_SMENUM_COALITION) return fail(BA_EINVAL, "form=%u", form);
-    char prefix[24];
-    snprintf(prefix, sizeof prefix, "form=%u ", form);
     const uint32_t B = p ? ba_smenum_bits(form, p->n, p->m, faulty_mask) : 0;
-    int rc = validate_enumeration(p, batch, "the SM enumeration", BA_MAX_DEPTH, faulty_mask, order, B, prefix,
-                                  [] { return (int)BA_OK; });
+    int rc = validate_enumeration(p, batch, "the SM enumeration", BA_MAX_DEPTH, faulty_mask, order, B,
+                                  EnumLead("form=%u ", form), enum_no_pre);
     if (rc != BA_OK) return rc;
     const SmenumShape s = smenum_shape(form, p->n, p->m, faulty_mask);
     g.form = form, g.n = p->n, g.m = p->m, g.me = s.me, g.fmask = s.F, g.order = order;
@@ -1919,9 +1979,8 @@ extern "C" int ba_smenum_run(ba_ctx* ctx, const ba_params* p, uint32_t form, uin
 // ---------------------------------------------------------------------------
 // The numbers of a case that its bit count and slot list are made of; ok = false:
 // bad coin, n, m or phases.
-struct RenumShape {
+struct RenumShape : CaseShape {
     bool ok = false;
-    uint32_t F = 0, nf = 0, ell = 0;
 };
 
 static RenumShape renum_shape(uint32_t coin, uint32_t n, uint32_t m, uint32_t phases, uint32_t faulty_mask) {
@@ -1929,10 +1988,8 @@ static RenumShape renum_shape(uint32_t coin, uint32_t n, uint32_t m, uint32_t ph
     if (coin > BA_RAND_COMMON || n < 1 || n > BA_MAX_GENERALS || m > kKing3MaxM || phases < 1 ||
         phases > BA_RENUM_MAX_PHASES)
         return s;
+    static_cast<CaseShape&>(s) = case_shape(n, faulty_mask);
     s.ok = true;
-    s.F = faulty_mask & general_mask(n);
-    s.nf = (uint32_t)__builtin_popcount(s.F);
-    s.ell = n - s.nf;
     return s;
 }
 
@@ -1951,35 +2008,20 @@ extern "C" int ba_renum_slots(uint32_t coin, uint32_t n, uint32_t m, uint32_t ph
                               uint32_t* part, uint32_t cap) {
     const RenumShape s = renum_shape(coin, n, m, phases, faulty_mask);
     if (!s.ok) return fail(BA_EINVAL, "coin=%u n=%u m=%u phases=%u", coin, n, m, phases);
-    const uint32_t B = ba_renum_bits(coin, n, m, phases, faulty_mask);
-    if (B > cap) return fail(BA_EINVAL, "cap=%u < %u free bits", cap, B);
-    if (B && (!q || !sender || !recipient || !part))
-        return fail(BA_EINVAL, "q, sender, recipient and part are required");
-    uint32_t bit = 0;
-    auto put = [&](uint32_t qq, uint32_t j, uint32_t i, uint32_t h) {
-        q[bit] = qq, sender[bit] = j, recipient[bit] = i, part[bit] = h;
-        ++bit;
-    };
-    // the free messages of round qq from sender j, in recipient order; parts bits each
-    auto round_of = [&](uint32_t qq, uint32_t j, uint32_t parts) {
-        if (!((s.F >> j) & 1u)) return;
-        for (uint32_t i = 0; i < n; ++i)
-            if (!((s.F >> i) & 1u))
-                for (uint32_t h = 0; h < parts; ++h) put(qq, j, i, h);
-    };
-    round_of(0, 0, 1);
+    SlotList sl{n, s.F, ba_renum_bits(coin, n, m, phases, faulty_mask), {q, sender, recipient, part}};
+    if (const int rc = sl.check(cap, "q, sender, recipient and part")) return rc;
+    sl.round_of(0, 0, 1);
     for (uint32_t p = 1; p <= phases; ++p) {
-        for (uint32_t j = 0; j < n; ++j) round_of(3 * p - 2, j, 1);
-        for (uint32_t j = 0; j < n; ++j) round_of(3 * p - 1, j, 2);
+        for (uint32_t j = 0; j < n; ++j) sl.round_of(3 * p - 2, j, 1);
+        for (uint32_t j = 0; j < n; ++j) sl.round_of(3 * p - 1, j, 2);
         if (coin == BA_RAND_COMMON) {
-            put(3 * p, 0xFFFFFFFFu, 0xFFFFFFFFu, 2);
+            sl.put(3 * p, 0xFFFFFFFFu, 0xFFFFFFFFu, 2);
         } else {
             for (uint32_t i = 0; i < n; ++i)
-                if (!((s.F >> i) & 1u)) put(3 * p, i, i, 2);
+                if (!((s.F >> i) & 1u)) sl.put(3 * p, i, i, 2);
         }
     }
-    if (bit != B) return fail(BA_EINVAL, "internal: %u free bits listed, formula %u", bit, B);
-    return (int)B;
+    return sl.close();
 }
 
 static int validate_renum(const ba_params* p, uint32_t coin, uint32_t phases, uint32_t faulty_mask,
@@ -1987,27 +2029,22 @@ static int validate_renum(const ba_params* p, uint32_t coin, uint32_t phases, ui
     if (coin > BA_RAND_COMMON) return fail(BA_EINVAL, "coin=%u", coin);
     if (phases < 1 || phases > BA_RENUM_MAX_PHASES)
         return fail(BA_EINVAL, "phases=%u outside [1,%d]", phases, BA_RENUM_MAX_PHASES);
-    char prefix[32];
-    snprintf(prefix, sizeof prefix, "coin=%u phases=%u ", coin, phases);
+    EnumLead lead("coin=%u phases=%u ", coin, phases);
+    lead.max_n = kRenumMaxN, lead.keeps = "k_renum keeps three planes";
     const uint32_t B = p ? ba_renum_bits(coin, p->n, p->m, phases, faulty_mask) : 0;
-    int rc = validate_enumeration(p, batch, "the RAND enumeration", kKing3MaxM, faulty_mask, order, B, prefix, [&] {
-        if (p->n > kRenumMaxN)
-            return fail(BA_ETOOBIG, "n=%u > %u: k_renum keeps three planes per general in registers", p->n,
-                        kRenumMaxN);
-        return (int)BA_OK;
-    });
+    int rc = validate_enumeration(p, batch, "the RAND enumeration", kKing3MaxM, faulty_mask, order, B, lead,
+                                  enum_no_pre);
     if (rc != BA_OK) return rc;
     const RenumShape s = renum_shape(coin, p->n, p->m, phases, faulty_mask);
     g.coin = coin, g.m = p->m, g.phases = phases, g.fmask = s.F, g.order = order;
     return BA_OK;
 }
 
-// launch(args, witness) of strategies from `first` on, whose per-trial decided bytes
+// One launch of a range of strategies from `first` on, whose per-trial decided bytes
 // start at `decided` (a launch range's later launches start further in)
-static auto renum_launch(const RenumCase& g, uint64_t first, uint8_t* decided, uint64_t* stats) {
-    return [&g, first, decided, stats](const RunArgs& a, uint64_t* w) {
-        return launch_renum(a, g, decided ? decided + (a.first_trial - first) : nullptr, w, stats);
-    };
+static hipError_t renum_launch(const RunArgs& a, const RenumCase& g, uint64_t first, uint8_t* decided,
+                               uint64_t* w, uint64_t* stats) {
+    return launch_renum(a, g, decided ? decided + (a.first_trial - first) : nullptr, w, stats);
 }
 
 extern "C" int ba_renum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t coin, uint32_t phases,
@@ -2019,50 +2056,26 @@ extern "C" int ba_renum_run_device(ba_ctx* ctx, const ba_params* p, uint32_t coi
     return enum_device_entry(
         ctx, p, batch, d_decisions, d_outcome, d_counters, d_witness, stream, nullptr,
         [&] { return validate_renum(p, coin, phases, faulty_mask, order, batch, g); }, enum_no_prepare,
-        [&](const RunArgs& a, uint64_t* w) {
-            return renum_launch(g, p->first_trial, d_decided, d_stats)(a, w);
-        });
+        [&](const RunArgs& a, uint64_t* w) { return renum_launch(a, g, p->first_trial, d_decided, w, d_stats); });
 }
 
-// enum_host_entry's shape with two additions: the decided bytes ride behind the
-// outcome in io_out (HostRun::extra), and the words after the counters are the
-// witness and the BA_RENUM_NSTATS stats, accumulated on the device across the chunks.
+// The decided bytes are the entry's one more plane, the BA_RENUM_NSTATS stats its words
+// after the witness: counts, but for the two witnesses among them.
 extern "C" int ba_renum_run(ba_ctx* ctx, const ba_params* p, uint32_t coin, uint32_t phases,
                             uint32_t faulty_mask, uint32_t order, uint64_t batch, uint64_t* decisions,
                             uint8_t* outcome, uint8_t* decided, ba_counters* counters, uint64_t* witness,
                             uint64_t* stats) {
-    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
     RenumCase g{};
-    int rc = validate_renum(p, coin, phases, faulty_mask, order, batch, g);
-    if (rc != BA_OK) return rc;
-    uint64_t tail[1 + BA_RENUM_NSTATS] = {};
-    tail[0] = tail[1 + 2] = tail[1 + 3] = UINT64_MAX;
-    auto give = [&] {
-        if (witness) *witness = tail[0];
-        if (stats) memcpy(stats, tail + 1, BA_RENUM_NSTATS * 8);
-    };
-    if (counters) memset(counters, 0, sizeof *counters);
-    give();
-    if (batch == 0) return BA_OK;
-    HostRun r;
-    r.decisions = decisions, r.outcome = outcome, r.counters = counters;
-    r.extra = decided, r.extra_elem = 1, r.extra_behind_dec = false;
-    r.tail = tail, r.tail_words = 1 + BA_RENUM_NSTATS;
-    r.tail_ones = 1u | (1u << (1 + 2)) | (1u << (1 + 3));
-    r.chunk_env = "BA_RENUM_HOST_CHUNK";
-    r.chunk = (decisions || outcome || decided) ? kHostChunk : batch;
-    r.before = [&](hipStream_t st) {
-        (void)ctx_mark(ctx, st);  // whatever follows: work of this ctx is queued on st
-        return (int)BA_OK;
-    };
-    r.queue = [&](const ba_params& q, uint64_t nt, const uint32_t*, const uint8_t*, uint64_t* d_dec,
-                  uint8_t* d_out, void* d_extra, uint64_t* d_cnt, hipStream_t st) {
-        return enum_launch_range(ctx, p, q.first_trial, nt, d_dec, d_out, d_cnt, d_cnt + BA_NCOUNTERS, st,
-                                 renum_launch(g, q.first_trial, (uint8_t*)d_extra, d_cnt + BA_NCOUNTERS + 1));
-    };
-    rc = host_run(ctx, p, batch, r);
-    if (rc == BA_OK) give();
-    return rc;
+    EnumHostMore more;
+    more.plane = decided, more.elem = 1;
+    more.words = stats, more.count = BA_RENUM_NSTATS, more.ones = (1u << 2) | (1u << 3);
+    return enum_host_entry(
+        ctx, p, batch, decisions, outcome, counters, witness, "BA_RENUM_HOST_CHUNK",
+        [&] { return validate_renum(p, coin, phases, faulty_mask, order, batch, g); }, enum_no_prepare,
+        [&](const RunArgs& a, uint64_t* w) {
+            return renum_launch(a, g, more.first, (uint8_t*)more.d_plane, w, w + 1);
+        },
+        &more);
 }
 
 extern "C" int ba_split_votes_device(ba_ctx* ctx, const ba_params* p, uint64_t batch,

@@ -1,8 +1,9 @@
-// ba_enum_common.hpp -- what the three exhaustive kernels share: k_enum (ba_enum.hip,
-// docs/SEMANTICS.md §8), k_kenum (ba_kenum.hip, §11) and k_smenum (ba_smenum.hip,
-// §12).  Trial t of a call is strategy S = t; one lane holds one 64-strategy word
-// w = S / 64, a free bit of the strategy index is a plane of it (enum_plane), and a
-// wave takes a tile of 64 consecutive words.
+// ba_enum_common.hpp -- what the four exhaustive kernels share: k_enum (ba_enum.hip,
+// docs/SEMANTICS.md §8), k_kenum (ba_kenum.hip, §11), k_smenum (ba_smenum.hip, §12)
+// and k_renum (ba_renum.hip, §14); what only the round-based two of them share is
+// ba_round_enum.hpp.  Trial t of a call is strategy S = t; one lane holds one
+// 64-strategy word w = S / 64, a free bit of the strategy index is a plane of it
+// (enum_plane), and a wave takes a tile of 64 consecutive words.
 //
 // enum_frame is everything around the evaluation of one word: the persistent tile
 // loop, the word's mask of strategies inside the call, the tally of the lieutenants'
@@ -41,6 +42,16 @@ __device__ __forceinline__ uint64_t enum_wave_sum(uint64_t x) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
     return x;
+}
+
+// x becomes the wave's smallest.  In place: taken and returned by value, the same
+// loop cost k_kenum and k_renum two VGPRs each, and two of them a wave per SIMD.
+__device__ __forceinline__ void enum_wave_min(uint64_t& x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t o = __shfl_xor(x, off, 64);
+        x = o < x ? o : x;
+    }
 }
 
 // One launch of a case, as the frame sees it.  me and inb: OM(m)'s depth for
@@ -210,11 +221,7 @@ __device__ __forceinline__ void enum_frame(const EnumRun& g, unsigned char* plan
         if (lane == (uint32_t)i) mine = tot[i];
     sink_counters(lane, mine, gwave, nwaves, g.counters, sk);
     if (g.witness) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint64_t o = __shfl_xor(wit, off, 64);
-            wit = o < wit ? o : wit;
-        }
+        enum_wave_min(wit);
         if (lane == 0 && wit != ~0ull) (void)atomicMin(g.witness, (unsigned long long)wit);
     }
 }

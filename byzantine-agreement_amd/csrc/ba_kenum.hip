@@ -5,90 +5,42 @@
 // trial t of a call is strategy S = t.  The kernel draws nothing, loads no
 // per-trial input and reads no table: there is nothing to upload.
 //
-// k_enum's stance (ba_enum.hip), not k_king's: one LANE holds one 64-strategy word
-// w = S / 64 and the n preference planes of its generals in registers (N is a
-// template parameter, so the plane arrays are never indexed dynamically); a wave
-// takes a tile of 64 consecutive words.  F, o, m and the phase are wave-uniform,
-// and with them the class of every message (truth / free / dead) and the index of
-// its free bit,
-//   base of the round + rank of the sender among the traitors * l
-//                     + rank of the recipient among the loyal      (l = n - |F|),
-// doubled in the propose round (lo, hi): SGPR arithmetic and scalar branches.
-//
-// A round's tally at recipient i splits into what every recipient sees alike, the
-// loyal senders' true values, counted once per round (`ls`), and what only i sees:
-//   i loyal    the |F| free planes addressed to it, by traitor rank
-//   i faulty   its own true value; the other traitors' messages are dead
-//              (retreat / no proposal) and add nothing
-// So the sender's identity never matters below, only its rank, and a recipient's
-// update needs nobody else's plane of the same round: preferences are updated in
-// place.  What the king of the phase shows (its majority / its x) is worked out
-// first, for the one general k = p - 1, with k's plane picked by uniform selects.
+// The lane = word stance, the numbering of the free bits and the split of a round's
+// tally into the loyal senders' sum and the recipient's own view are
+// ba_round_enum.hpp's; the planes here are the n preferences.  What the king of the
+// phase shows (its majority / its x) is worked out first, for the one general
+// k = p - 1, with k's plane picked by uniform selects.
 //
 // The tile loop, the counters, the witness and the per-trial outputs are the frame
 // of ba_enum_common.hpp; the word evaluator below hands it the lieutenants' planes.
-#include "ba_enum_common.hpp"
-
-#include <utility>
+#include "ba_round_enum.hpp"
 
 namespace ba {
-
-using KCount = Count<5>;  // a tally of at most 16 messages
-
-// The case (uniform over the launch) and the lane's word.
-struct KenumWord {
-    uint32_t F, nf, ell;  // the faulty mask, |F|, the loyal generals
-    uint32_t m;
-    uint32_t wlo, whi;  // this lane's word index w = S / 64
-};
-
-// rank of general i among the loyal ones
-__device__ __forceinline__ uint32_t kenum_lrank(const KenumWord& c, uint32_t i) {
-    return (uint32_t)__popc(~c.F & ((1u << i) - 1u));
-}
-
-// `ls` plus what recipient i alone is shown in a one-bit round whose free bits
-// start at `base`: mine = i's own true value (i faulty), rl = i's loyal rank
-__device__ __forceinline__ KCount kenum_votes(const KenumWord& c, const KCount& ls, bool fi,
-                                              uint64_t mine, uint32_t base, uint32_t rl) {
-    KCount t = ls;
-    if (fi) {
-        t.add(mine);
-    } else {
-        for (uint32_t rf = 0; rf < c.nf; ++rf) t.add(enum_plane(base + rf * c.ell + rl, c.wlo, c.whi));
-    }
-    return t;
-}
 
 // KING3's proposal of a general that counted c1 attack votes: R = [c1 <= m],
 // A = [c1 >= n - m] and not R (retreat wins when both hold)
 template <int N>
-__device__ __forceinline__ void king3_proposal(const KenumWord& c, const KCount& c1, uint64_t& A,
-                                               uint64_t& R) {
-    const uint32_t Tq = (uint32_t)N > c.m ? (uint32_t)N - c.m : 0u;
-    R = ~c1.ge(c.m + 1u);
+__device__ __forceinline__ void king3_proposal(uint32_t m, const RoundCount& c1, uint64_t& A, uint64_t& R) {
+    const uint32_t Tq = (uint32_t)N > m ? (uint32_t)N - m : 0u;
+    R = ~c1.ge(m + 1u);
     A = c1.ge(Tq) & ~R;
 }
 
 // KING3's propose round at recipient i: x and sure.  lsA / lsR: the loyal senders'
 // proposals; ownA / ownR: i's own (i faulty); pbase: the round's first free bit.
 template <int N>
-__device__ __forceinline__ void king3_propose(const KenumWord& c, const KCount& lsA, const KCount& lsR,
-                                              bool fi, uint64_t ownA, uint64_t ownR, uint64_t pref,
-                                              uint32_t pbase, uint32_t rl, uint64_t& x, uint64_t& sure) {
-    KCount d1 = lsA, d0 = lsR;
+__device__ __forceinline__ void king3_propose(const RoundWord& c, uint32_t m, const RoundCount& lsA,
+                                              const RoundCount& lsR, bool fi, uint64_t ownA, uint64_t ownR,
+                                              uint64_t pref, uint32_t pbase, uint32_t rl, uint64_t& x,
+                                              uint64_t& sure) {
+    RoundCount d1 = lsA, d0 = lsR;
     if (fi) {
         d1.add(ownA);
         d0.add(ownR);
     } else {
-        for (uint32_t rf = 0; rf < c.nf; ++rf) {
-            const uint32_t b = pbase + 2u * (rf * c.ell + rl);
-            const uint64_t lo = enum_plane(b, c.wlo, c.whi), hi = enum_plane(b + 1u, c.wlo, c.whi);
-            d1.add(lo & hi);   // lo = 1: the proposal is hi
-            d0.add(lo & ~hi);  // lo = 0: no proposal, whatever hi is
-        }
+        round_proposals(c, d1, d0, pbase, rl);
     }
-    const uint32_t Tq = (uint32_t)N > c.m ? (uint32_t)N - c.m : 0u, Tm = c.m + 1u;
+    const uint32_t Tq = (uint32_t)N > m ? (uint32_t)N - m : 0u, Tm = m + 1u;
     const uint64_t x0 = d0.ge(Tm), x1 = d1.ge(Tm);
     x = ~x0 & (x1 | pref);
     sure = (x & d1.ge(Tq)) | (~x & d0.ge(Tq));
@@ -107,22 +59,19 @@ __device__ __forceinline__ uint64_t kenum_pick(const uint64_t (&pref)[N], uint32
 // One Phase King phase (§9) over the word, king k; base: the exchange round's
 // first free bit, advanced past the phase.
 template <int N>
-__device__ __forceinline__ void kenum_king_phase(const KenumWord& c, uint64_t (&pref)[N], uint32_t k,
-                                                 uint32_t& base) {
-    const uint32_t S = ((uint32_t)N + 2u * c.m) / 2u + 1u, Tmaj = (uint32_t)N / 2u + 1u;
+__device__ __forceinline__ void kenum_king_phase(const RoundWord& c, uint32_t m, uint64_t (&pref)[N],
+                                                 uint32_t k, uint32_t& base) {
+    const uint32_t S = ((uint32_t)N + 2u * m) / 2u + 1u, Tmaj = (uint32_t)N / 2u + 1u;
     const uint32_t xbase = base, kbase = base + c.nf * c.ell;
     const bool Fk = ((c.F >> k) & 1u) != 0;
-    KCount ls;
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-        if (!((c.F >> j) & 1u)) ls.add(pref[j]);
+    const RoundCount ls = round_loyal(c, pref);
     // the king's own majority
-    const uint64_t kmaj = kenum_votes(c, ls, Fk, kenum_pick<N>(pref, k), xbase, kenum_lrank(c, k)).ge(Tmaj);
+    const uint64_t kmaj = round_votes(c, ls, Fk, kenum_pick<N>(pref, k), xbase, round_lrank(c, k)).ge(Tmaj);
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         const bool fi = ((c.F >> i) & 1u) != 0;
-        const uint32_t rl = kenum_lrank(c, (uint32_t)i);
-        const KCount c1 = kenum_votes(c, ls, fi, pref[i], xbase, rl);
+        const uint32_t rl = round_lrank(c, (uint32_t)i);
+        const RoundCount c1 = round_votes(c, ls, fi, pref[i], xbase, rl);
         const uint64_t hi = c1.ge(S), lo = S <= (uint32_t)N ? ~c1.ge((uint32_t)N - S + 1u) : 0ull;
         uint64_t km = kmaj;  // i = k, or a loyal king
         if (Fk && k != (uint32_t)i) km = fi ? 0ull : enum_plane(kbase + rl, c.wlo, c.whi);
@@ -133,22 +82,19 @@ __device__ __forceinline__ void kenum_king_phase(const KenumWord& c, uint64_t (&
 
 // One KING3 phase (§10) over the word, king k.
 template <int N>
-__device__ __forceinline__ void kenum_king3_phase(const KenumWord& c, uint64_t (&pref)[N], uint32_t k,
-                                                  uint32_t& base) {
+__device__ __forceinline__ void kenum_king3_phase(const RoundWord& c, uint32_t m, uint64_t (&pref)[N],
+                                                  uint32_t k, uint32_t& base) {
     const uint32_t vbase = base, pbase = vbase + c.nf * c.ell, kbase = pbase + 2u * c.nf * c.ell;
     const bool Fk = ((c.F >> k) & 1u) != 0;
-    KCount lsV;
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-        if (!((c.F >> j) & 1u)) lsV.add(pref[j]);
+    const RoundCount lsV = round_loyal(c, pref);
     // value round: the loyal generals' proposals, counted once (a faulty general's
     // own proposal is worked out again where it is counted, in its propose round)
-    KCount lsA, lsR;
+    RoundCount lsA, lsR;
 #pragma unroll
     for (int j = 0; j < N; ++j) {
         if (!((c.F >> j) & 1u)) {
             uint64_t A, R;
-            king3_proposal<N>(c, kenum_votes(c, lsV, false, 0, vbase, kenum_lrank(c, (uint32_t)j)), A, R);
+            king3_proposal<N>(m, round_votes(c, lsV, false, 0, vbase, round_lrank(c, (uint32_t)j)), A, R);
             lsA.add(A);
             lsR.add(R);
         }
@@ -158,17 +104,17 @@ __device__ __forceinline__ void kenum_king3_phase(const KenumWord& c, uint64_t (
     {
         const uint64_t pk = kenum_pick<N>(pref, k);
         uint64_t A = 0, R = 0;
-        if (Fk) king3_proposal<N>(c, kenum_votes(c, lsV, true, pk, vbase, 0), A, R);
-        king3_propose<N>(c, lsA, lsR, Fk, A, R, pk, pbase, kenum_lrank(c, k), kx, ksure);
+        if (Fk) king3_proposal<N>(m, round_votes(c, lsV, true, pk, vbase, 0), A, R);
+        king3_propose<N>(c, m, lsA, lsR, Fk, A, R, pk, pbase, round_lrank(c, k), kx, ksure);
     }
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         const bool fi = ((c.F >> i) & 1u) != 0;
-        const uint32_t rl = kenum_lrank(c, (uint32_t)i);
+        const uint32_t rl = round_lrank(c, (uint32_t)i);
         uint64_t A = 0, R = 0;
-        if (fi) king3_proposal<N>(c, kenum_votes(c, lsV, true, pref[i], vbase, 0), A, R);
+        if (fi) king3_proposal<N>(m, round_votes(c, lsV, true, pref[i], vbase, 0), A, R);
         uint64_t x, sure;
-        king3_propose<N>(c, lsA, lsR, fi, A, R, pref[i], pbase, rl, x, sure);
+        king3_propose<N>(c, m, lsA, lsR, fi, A, R, pref[i], pbase, rl, x, sure);
         uint64_t km = kx;  // i = k (then km = x), or a loyal king
         if (Fk && k != (uint32_t)i) km = fi ? 0ull : enum_plane(kbase + rl, c.wlo, c.whi);
         pref[i] = (sure & x) | (~sure & km);
@@ -186,47 +132,34 @@ __global__ __launch_bounds__(kEnumThreads) void k_kenum(KenumCase g, uint64_t fi
                                                         Sink sk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char kenum_lds[];
     constexpr uint32_t n = (uint32_t)N;
-    KenumWord c;
-    c.F = g.fmask;
-    c.nf = (uint32_t)__popc(g.fmask);
-    c.ell = n - c.nf;
-    c.m = g.m;
     const bool F0 = (g.fmask & 1u) != 0;
     const uint64_t ob = g.order == 1u ? ~0ull : 0ull;
     // in-bound is the protocol's
-    const bool inb = c.nf <= g.m && n > (PROTO == 0 ? 4u : 3u) * g.m;
+    const bool inb = (uint32_t)__popc(g.fmask) <= g.m && n > (PROTO == 0 ? 4u : 3u) * g.m;
     const EnumRun run{n, g.fmask, g.order, 0u, inb, first_trial, batch, decisions, outcome, counters, witness};
     enum_frame<false, true>(run, kenum_lds, sk, [&](uint32_t wlo, uint32_t whi, EnumTally<false>& ty) {
-        c.wlo = wlo;
-        c.whi = whi;
-        // round 0: the commander sends
+        const RoundWord c = round_word(g.fmask, n, wlo, whi);
+        // round 0: the commander sends (spelled out here and in k_renum: as a shared
+        // helper it cost k_kenum<0, 2> two VGPRs and with them a wave per SIMD)
         uint64_t pref[N];
         pref[0] = ob;
 #pragma unroll
         for (int i = 1; i < N; ++i) {
             if (!F0) pref[i] = ob;
             else if ((c.F >> i) & 1u) pref[i] = 0;  // dead
-            else pref[i] = enum_plane(kenum_lrank(c, (uint32_t)i), c.wlo, c.whi);
+            else pref[i] = enum_plane(round_lrank(c, (uint32_t)i), c.wlo, c.whi);
         }
         uint32_t base = F0 ? c.ell : 0u;
         for (uint32_t p = 1; p <= g.phases; ++p) {
-            if constexpr (PROTO == 0) kenum_king_phase<N>(c, pref, p - 1u, base);
-            else kenum_king3_phase<N>(c, pref, p - 1u, base);
+            if constexpr (PROTO == 0) kenum_king_phase<N>(c, g.m, pref, p - 1u, base);
+            else kenum_king3_phase<N>(c, g.m, pref, p - 1u, base);
         }
-        // decisions = the lieutenants' preferences; never undefined
-#pragma unroll
-        for (int r = 1; r < N; ++r) ty.put((uint32_t)(r - 1), !((c.F >> r) & 1u), pref[r]);
+        round_decide(c, pref, ty);
     });
 }
 
 using KenumKernel = void (*)(KenumCase, uint64_t, uint64_t, uint64_t*, uint8_t*, uint64_t*,
                              unsigned long long*, Sink);
-
-template <int PROTO, size_t... I>
-static KenumKernel kenum_kernel_of(uint32_t n, std::index_sequence<I...>) {
-    static constexpr KenumKernel tab[] = {k_kenum<PROTO, (int)I + 1>...};
-    return tab[n - 1u];
-}
 
 // One persistent launch of enum_geometry's shape (at most 7.5 KiB of decision planes).
 hipError_t launch_kenum(const RunArgs& a, const KenumCase& g, uint64_t* witness) {
@@ -234,8 +167,9 @@ hipError_t launch_kenum(const RunArgs& a, const KenumCase& g, uint64_t* witness)
         return hipErrorInvalidValue;
     const EnumGeometry ge = enum_geometry(a, (uint32_t)sizeof(EnumEntry<false>), 0u);
     ProfScope ps(a.prof, "k_kenum", a.stream);
-    const KenumKernel k = g.proto == 0 ? kenum_kernel_of<0>(a.n, std::make_index_sequence<kKenumMaxN>{})
-                                       : kenum_kernel_of<1>(a.n, std::make_index_sequence<kKenumMaxN>{});
+    const KenumKernel k = round_kernel_of<kKenumMaxN>(a.n, [&](auto N) -> KenumKernel {
+        return g.proto == 0 ? k_kenum<0, decltype(N)::value> : k_kenum<1, decltype(N)::value>;
+    });
     hipLaunchKernelGGL(k, dim3(ge.blocks), dim3(ge.threads), ge.lds, a.stream, g, a.first_trial, a.batch,
                        a.decisions, a.outcome, a.counters, (unsigned long long*)witness, a.sink);
     return hipGetLastError();

@@ -7,18 +7,11 @@
 // of a call is strategy S = t, so a walk of the space covers every play of every
 // adversary, the one that sees the coins included.  Nothing is drawn or loaded.
 //
-// k_kenum's stance (ba_kenum.hip): one LANE holds one 64-strategy word w = S / 64 and
-// the planes x, D, V of its N generals in registers (N is a template parameter, so
-// the arrays are never indexed dynamically); F, m, the phase, the class of every
-// message and the index of its free bit are wave-uniform SGPR arithmetic:
-//   report   base + rf l + rl          rf: the sender's rank among the traitors
-//   propose  base + 2 (rf l + rl)      rl: the recipient's rank among the loyal
-//   toss     base + rl (LOCAL), base (COMMON)
-// A round's tally at recipient i is what every recipient sees alike, the loyal
-// senders' true values counted once per round (ls; lsA, lsR), plus what only i sees:
-// its |F| free planes (i loyal) or its own true value (i faulty; the other traitors'
-// messages to it are dead and add nothing).  A faulty general's D and V reach no
-// output and stay zero.
+// The lane = word stance, the numbering of a message's free bit and the split of a
+// round's tally into the loyal senders' sum and the recipient's own view are
+// ba_round_enum.hpp's; the planes here are x, D, V of the N generals, and a phase's
+// toss bits follow its proposals: base + rl (LOCAL), base (COMMON).  A faulty
+// general's D and V reach no output and stay zero.
 //
 // `decided` on planes: a sticky unsafe plane built from §13's three conditions at the
 // end of every phase, a sticky all-loyal-decided plane, and the phase of the latter's
@@ -26,49 +19,25 @@
 // and the decisions / outcome pick-out are the frame of ba_enum_common.hpp; the stats
 // are per-lane sums in what the word evaluator captures, reduced once per wave after
 // the frame returns.
-#include "ba_enum_common.hpp"
-
-#include <utility>
+#include "ba_round_enum.hpp"
 
 namespace ba {
-
-using RCount = Count<5>;  // a tally of at most 16 messages
-
-struct RenumWord {
-    uint32_t F, nf, ell;  // the faulty mask, |F|, the loyal generals
-    uint32_t wlo, whi;    // this lane's word index w = S / 64
-};
-
-__device__ __forceinline__ uint32_t renum_lrank(const RenumWord& c, uint32_t i) {
-    return (uint32_t)__popc(~c.F & ((1u << i) - 1u));
-}
-
-// `ls` plus recipient i's |F| free report planes (i loyal, rank rl)
-__device__ __forceinline__ RCount renum_reports(const RenumWord& c, const RCount& ls, uint32_t base,
-                                                uint32_t rl) {
-    RCount t = ls;
-    for (uint32_t rf = 0; rf < c.nf; ++rf) t.add(enum_plane(base + rf * c.ell + rl, c.wlo, c.whi));
-    return t;
-}
 
 // One phase (§13) over the word.  base: the report round's first free bit, advanced
 // past the phase's toss bits.
 template <bool COMMON, int N>
-__device__ __forceinline__ void renum_phase(const RenumWord& c, uint32_t T, uint32_t Tm, uint64_t (&x)[N],
+__device__ __forceinline__ void renum_phase(const RoundWord& c, uint32_t T, uint32_t Tm, uint64_t (&x)[N],
                                             uint64_t (&D)[N], uint64_t (&V)[N], uint32_t& base) {
     const uint32_t rbase = base, pbase = rbase + c.nf * c.ell, tbase = pbase + 2u * c.nf * c.ell;
     const uint32_t Tr = (uint32_t)N - T + 1u;  // c0 >= T  <=>  c1 <= n - T  <=>  not c1 >= Tr (T <= n)
-    RCount ls;
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-        if (!((c.F >> j) & 1u)) ls.add(x[j]);
+    const RoundCount ls = round_loyal(c, x);
     // report: the loyal generals' proposals, counted once (a faulty general's own is
     // worked out where it is counted, in its propose round)
-    RCount lsA, lsR;
+    RoundCount lsA, lsR;
 #pragma unroll
     for (int j = 0; j < N; ++j) {
         if (!((c.F >> j) & 1u)) {
-            const RCount c1 = renum_reports(c, ls, rbase, renum_lrank(c, (uint32_t)j));
+            const RoundCount c1 = round_votes(c, ls, false, 0, rbase, round_lrank(c, (uint32_t)j));
             lsA.add(c1.ge(T));
             lsR.add(T <= (uint32_t)N ? ~c1.ge(Tr) : 0ull);
         }
@@ -77,21 +46,15 @@ __device__ __forceinline__ void renum_phase(const RenumWord& c, uint32_t T, uint
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         const bool fi = ((c.F >> i) & 1u) != 0;
-        const uint32_t rl = renum_lrank(c, (uint32_t)i);
-        RCount d1 = lsA, d0 = lsR;
+        const uint32_t rl = round_lrank(c, (uint32_t)i);
+        RoundCount d1 = lsA, d0 = lsR;
         uint64_t coin = common;
         if (fi) {
-            RCount c1 = ls;
-            c1.add(x[i]);
+            const RoundCount c1 = round_votes(c, ls, true, x[i], rbase, 0);
             d1.add(c1.ge(T));
             d0.add(T <= (uint32_t)N ? ~c1.ge(Tr) : 0ull);
         } else {
-            for (uint32_t rf = 0; rf < c.nf; ++rf) {
-                const uint32_t b = pbase + 2u * (rf * c.ell + rl);
-                const uint64_t lo = enum_plane(b, c.wlo, c.whi), hi = enum_plane(b + 1u, c.wlo, c.whi);
-                d1.add(lo & hi);   // lo = 1: the proposal is hi
-                d0.add(lo & ~hi);  // lo = 0: no proposal, whatever hi is
-            }
+            round_proposals(c, d1, d0, pbase, rl);
             if (!COMMON) coin = enum_plane(tbase + rl, c.wlo, c.whi);
         }
         const uint64_t v0 = d0.ge(Tm), v1 = d1.ge(Tm) & ~v0;
@@ -115,14 +78,10 @@ __global__ __launch_bounds__(kEnumThreads) void k_renum(RenumCase g, uint64_t fi
                                                         unsigned long long* __restrict__ stats, Sink sk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char renum_lds[];
     constexpr uint32_t n = (uint32_t)N;
-    RenumWord c;
-    c.F = g.fmask;
-    c.nf = (uint32_t)__popc(g.fmask);
-    c.ell = n - c.nf;
     const bool F0 = (g.fmask & 1u) != 0;
     const uint64_t ob = g.order == 1u ? ~0ull : 0ull;
     const uint32_t T = (n + g.m) / 2u + 1u, Tm = g.m + 1u;
-    const bool inb = c.nf <= g.m && n > 3u * g.m;
+    const bool inb = (uint32_t)__popc(g.fmask) <= g.m && n > 3u * g.m;
     // per-lane stats: unsafe, undecided, their smallest S, decided in phase p
     uint32_t sUns = 0, sUnd = 0, sIn[kRenumMaxPhases];
 #pragma unroll
@@ -130,20 +89,19 @@ __global__ __launch_bounds__(kEnumThreads) void k_renum(RenumCase g, uint64_t fi
     uint64_t wUns = ~0ull, wUnd = ~0ull;
     const EnumRun run{n, g.fmask, g.order, 0u, inb, first_trial, batch, decisions, outcome, counters, witness};
     enum_frame<false, true>(run, renum_lds, sk, [&](uint32_t wlo, uint32_t whi, EnumTally<false>& ty) {
-        c.wlo = wlo;
-        c.whi = whi;
-        // round 0: the commander sends
+        const RoundWord c = round_word(g.fmask, n, wlo, whi);
+        // round 0: the commander sends (as in k_kenum, which says why it is spelled out)
         uint64_t x[N], D[N], V[N];
         x[0] = ob;
 #pragma unroll
         for (int i = 1; i < N; ++i) {
             if (!F0) x[i] = ob;
             else if ((c.F >> i) & 1u) x[i] = 0;  // dead
-            else x[i] = enum_plane(renum_lrank(c, (uint32_t)i), c.wlo, c.whi);
+            else x[i] = enum_plane(round_lrank(c, (uint32_t)i), c.wlo, c.whi);
         }
+        uint32_t base = F0 ? c.ell : 0u;
 #pragma unroll
         for (int i = 0; i < N; ++i) D[i] = V[i] = 0;
-        uint32_t base = F0 ? c.ell : 0u;
         uint64_t bad = 0, seen = 0, ph[5] = {0, 0, 0, 0, 0};
         for (uint32_t p = 1; p <= g.phases; ++p) {
             renum_phase<COMMON, N>(c, T, Tm, x, D, V, base);
@@ -164,9 +122,7 @@ __global__ __launch_bounds__(kEnumThreads) void k_renum(RenumCase g, uint64_t fi
             for (int b = 0; b < 5; ++b)
                 if ((p >> b) & 1u) ph[b] |= first;
         }
-        // decisions = the lieutenants' preferences; never undefined
-#pragma unroll
-        for (int r = 1; r < N; ++r) ty.put((uint32_t)(r - 1), !((c.F >> r) & 1u), x[r]);
+        round_decide(c, x, ty);
         const uint64_t lm = ty.lm, gw = ((uint64_t)whi << 32) | wlo;
         const uint64_t uns = bad & lm, und = ~bad & ~seen & lm, in = ~bad & seen & lm;
         sUns += (uint32_t)__popcll(uns);
@@ -214,12 +170,8 @@ __global__ __launch_bounds__(kEnumThreads) void k_renum(RenumCase g, uint64_t fi
             const uint64_t t = enum_wave_sum(sIn[p]);
             if (lane == (uint32_t)(4 + p)) mine = t;
         }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const uint64_t o1 = __shfl_xor(wUns, off, 64), o2 = __shfl_xor(wUnd, off, 64);
-            wUns = o1 < wUns ? o1 : wUns;
-            wUnd = o2 < wUnd ? o2 : wUnd;
-        }
+        enum_wave_min(wUns);
+        enum_wave_min(wUnd);
         if (lane == 2 || lane == 3) {
             const uint64_t w = lane == 2 ? wUns : wUnd;
             if (w != ~0ull) (void)atomicMin(stats + lane, (unsigned long long)w);
@@ -232,12 +184,6 @@ __global__ __launch_bounds__(kEnumThreads) void k_renum(RenumCase g, uint64_t fi
 using RenumKernel = void (*)(RenumCase, uint64_t, uint64_t, uint64_t*, uint8_t*, uint8_t*, uint64_t*,
                              unsigned long long*, unsigned long long*, Sink);
 
-template <bool COMMON, size_t... I>
-static RenumKernel renum_kernel_of(uint32_t n, std::index_sequence<I...>) {
-    static constexpr RenumKernel tab[] = {k_renum<COMMON, (int)I + 1>...};
-    return tab[n - 1u];
-}
-
 // One persistent launch of enum_geometry's shape (at most 7.5 KiB of decision planes).
 hipError_t launch_renum(const RunArgs& a, const RenumCase& g, uint8_t* decided, uint64_t* witness,
                         uint64_t* stats) {
@@ -246,8 +192,9 @@ hipError_t launch_renum(const RunArgs& a, const RenumCase& g, uint8_t* decided, 
         return hipErrorInvalidValue;
     const EnumGeometry ge = enum_geometry(a, (uint32_t)sizeof(EnumEntry<false>), 0u);
     ProfScope ps(a.prof, "k_renum", a.stream);
-    const RenumKernel k = g.coin == 1 ? renum_kernel_of<true>(a.n, std::make_index_sequence<kRenumMaxN>{})
-                                      : renum_kernel_of<false>(a.n, std::make_index_sequence<kRenumMaxN>{});
+    const RenumKernel k = round_kernel_of<kRenumMaxN>(a.n, [&](auto N) -> RenumKernel {
+        return g.coin == 1 ? k_renum<true, decltype(N)::value> : k_renum<false, decltype(N)::value>;
+    });
     hipLaunchKernelGGL(k, dim3(ge.blocks), dim3(ge.threads), ge.lds, a.stream, g, a.first_trial, a.batch,
                        a.decisions, a.outcome, decided, a.counters, (unsigned long long*)witness,
                        (unsigned long long*)stats, a.sink);
