@@ -35,6 +35,7 @@ KING_UNSETTLED = 255  # RunResult.settled: the loyal generals differ after the l
 RAND_LOCAL, RAND_COMMON = 0, 1  # run_rand's coin: each general's own, or one per trial (docs/SEMANTICS.md §13)
 RAND_MAX_PHASES = 64
 RAND_UNDECIDED, RAND_UNSAFE = 255, 254  # RunResult.decided beside a phase number 1..R
+RSTALL_MAX_PHASES = 250  # run_rstall's phases (docs/SEMANTICS.md §15)
 COUNTER_NAMES = ["trials", "agreement", "validity_applicable", "validity", "quorum_retreat",
                  "quorum_attack", "quorum_undetermined", "undefined_decisions", "in_bound",
                  "bound_violations", "faulty_total", "attack_decisions"]
@@ -57,6 +58,7 @@ EXPORTS = ["ba_version", "ba_device_count", "ba_ctx_create", "ba_ctx_destroy", "
            "ba_king_phases", "ba_king3_run_trials", "ba_king3_run_trials_device",
            "ba_king3_coin_calls", "ba_king3_phases",
            "ba_rand_run_trials", "ba_rand_run_trials_device", "ba_rand_coin_calls",
+           "ba_rstall_run_trials", "ba_rstall_run_trials_device", "ba_rstall_coin_calls",
            "ba_kenum_bits", "ba_kenum_slots", "ba_kenum_run", "ba_kenum_run_device",
            "ba_smenum_bits", "ba_smenum_slots", "ba_smenum_run", "ba_smenum_run_device",
            "ba_renum_bits", "ba_renum_slots", "ba_renum_run", "ba_renum_run_device"]
@@ -226,6 +228,12 @@ def load(path: str | None = None):
                                               vp, vp, vp, vp, vp]
     lib.ba_rand_coin_calls.argtypes = [u32, u32, u32]
     lib.ba_rand_coin_calls.restype = u64
+    lib.ba_rstall_run_trials.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u64, vp, vp, vp, vp, vp,
+                                         ctypes.POINTER(Counters)]
+    lib.ba_rstall_run_trials_device.argtypes = [vp, ctypes.POINTER(Params), u32, u32, u64, vp, vp, vp,
+                                                vp, vp, vp, vp]
+    lib.ba_rstall_coin_calls.argtypes = [u32, u32, u32]
+    lib.ba_rstall_coin_calls.restype = u64
     lib.ba_kenum_bits.argtypes = [u32, u32, u32, u32]
     lib.ba_kenum_bits.restype = u32
     lib.ba_kenum_slots.argtypes = [u32, u32, u32, u32, vp, vp, vp, vp, u32]
@@ -481,6 +489,30 @@ class Engine:
         asynchronous, counters accumulated."""
         _check(self.lib, self.lib.ba_rand_run_trials_device(
             self.handle, ctypes.byref(params), policy, coin, phases, batch, d_faulty or None,
+            d_order or None, d_decisions or None, d_outcome or None, d_decided or None,
+            d_counters or None, stream or None))
+
+    def run_rstall(self, n, m, batch, phases, coin=RAND_COMMON, seed=0, lie_mode=LIE_PHILOX,
+                   faulty_mode=FAULTY_GIVEN, f=0, order_mode=ORDER_GIVEN, order_value=ATTACK,
+                   engine=ENGINE_AUTO, first_trial=0, faulty=None, order=None, want_decisions=True,
+                   want_outcome=True, want_decided=False) -> RunResult:
+        """Resolve `batch` trials of randomized agreement against the stalling adversary
+        (`phases` of them, up to RSTALL_MAX_PHASES; coin RAND_LOCAL / RAND_COMMON;
+        docs/SEMANTICS.md §15; m <= 10) through host buffers; the same inputs as `run_rand`
+        with equal keywords."""
+        params = (n, m, seed, lie_mode, faulty_mode, f, order_mode, order_value, engine, first_trial)
+        dec, out, cnt, dcd = self._run_protocol(self.lib.ba_rstall_run_trials, (coin, phases), params,
+                                                batch, faulty, order, want_decisions, want_outcome,
+                                                (np.uint8, want_decided))
+        return RunResult(dec, out, cnt, decided=dcd)
+
+    def run_rstall_device(self, params: Params, batch: int, phases: int, coin: int = RAND_COMMON,
+                          d_faulty=0, d_order=0, d_decisions=0, d_outcome=0, d_decided=0,
+                          d_counters=0, stream=0):
+        """Enqueue stalling-adversary trials on device pointers (ba_rstall_run_trials_device);
+        asynchronous, counters accumulated."""
+        _check(self.lib, self.lib.ba_rstall_run_trials_device(
+            self.handle, ctypes.byref(params), coin, phases, batch, d_faulty or None,
             d_order or None, d_decisions or None, d_outcome or None, d_decided or None,
             d_counters or None, stream or None))
 
@@ -879,6 +911,12 @@ def rand_coin_calls(n: int, phases: int, coin: int) -> int:
     """Philox calls per 64-trial word of k_rand when every sender is faulty in the word and
     every toss is drawn (ba_rand_coin_calls); 0 for bad arguments."""
     return int(load().ba_rand_coin_calls(n, phases, coin))
+
+
+def rstall_coin_calls(n: int, phases: int, coin: int) -> int:
+    """Philox calls per 64-trial word of k_rstall when every toss is drawn
+    (ba_rstall_coin_calls); 0 for bad arguments."""
+    return int(load().ba_rstall_coin_calls(n, phases, coin))
 
 
 def king3_phases(n: int, m: int) -> int:

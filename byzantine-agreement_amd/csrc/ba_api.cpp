@@ -1039,7 +1039,7 @@ extern "C" int ba_run_trials_device(ba_ctx* ctx, const ba_params* p, uint64_t ba
 }
 
 // ---------------------------------------------------------------------------
-// The wave protocols beside OM(m): SM, ADV, KING, KING3, RAND and the enumerations.  A
+// The wave protocols beside OM(m): SM, ADV, KING, KING3, RAND, RSTALL and the enumerations.  A
 // protocol is its validation tail (validate_protocol plus what only it checks), a
 // device entry (protocol_device_entry with its launch; the enumerations':
 // enum_device_entry) and a host entry (host_run with a HostRun that says what it
@@ -1439,6 +1439,60 @@ extern "C" int ba_rand_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t poli
                   uint64_t* d_dec, uint8_t* d_out, void* d_extra, uint64_t* d_cnt, hipStream_t st) {
         return ba_rand_run_trials_device(ctx, &q, policy, coin, phases, nt, d_f, d_o, d_dec, d_out,
                                          (uint8_t*)d_extra, d_cnt, st);
+    };
+    return host_run(ctx, p, batch, r);
+}
+
+// ---------------------------------------------------------------------------
+// RAND against the stalling adversary (docs/SEMANTICS.md §15; ba_rstall.hip)
+// ---------------------------------------------------------------------------
+// no message coin: the tosses alone, one call per general (LOCAL) or per word (COMMON)
+// and phase
+extern "C" uint64_t ba_rstall_coin_calls(uint32_t n, uint32_t phases, uint32_t coin) {
+    if (n < 1 || n > BA_MAX_GENERALS || phases < 1 || phases > BA_RSTALL_MAX_PHASES || coin > BA_RAND_COMMON)
+        return 0;
+    return (uint64_t)phases * (coin == BA_RAND_LOCAL ? n : 1);
+}
+
+static int validate_rstall(const ba_params* p, uint32_t coin, uint32_t phases, uint64_t batch,
+                           bool has_faulty, bool has_order) {
+    int rc = validate_protocol(p, batch, has_faulty, has_order, "RAND", kKing3MaxM);
+    if (rc != BA_OK) return rc;
+    if (coin > BA_RAND_COMMON) return fail(BA_EINVAL, "coin=%u", coin);
+    if (phases < 1 || phases > BA_RSTALL_MAX_PHASES)
+        return fail(BA_EINVAL, "phases=%u outside [1,%d]", phases, BA_RSTALL_MAX_PHASES);
+    return BA_OK;
+}
+
+extern "C" int ba_rstall_run_trials_device(ba_ctx* ctx, const ba_params* p, uint32_t coin,
+                                           uint32_t phases, uint64_t batch, const uint32_t* d_faulty,
+                                           const uint8_t* d_order, uint64_t* d_decisions,
+                                           uint8_t* d_outcome, uint8_t* d_decided, uint64_t* d_counters,
+                                           void* stream) {
+    return protocol_device_entry(
+        ctx, p, batch, d_faulty, d_order, d_decisions, d_outcome, d_counters, stream,
+        [&] { return validate_rstall(p, coin, phases, batch, d_faulty != nullptr, d_order != nullptr); },
+        [&](const RunArgs& a) { return launch_rstall(a, coin, phases, d_decided); });
+}
+
+// outcome and decided bytes share io_out, as RAND's
+extern "C" int ba_rstall_run_trials(ba_ctx* ctx, const ba_params* p, uint32_t coin, uint32_t phases,
+                                    uint64_t batch, const uint32_t* faulty, const uint8_t* order,
+                                    uint64_t* decisions, uint8_t* outcome, uint8_t* decided,
+                                    ba_counters* counters) {
+    if (!ctx) return fail(BA_EINVAL, "ctx is NULL");
+    int rc = validate_rstall(p, coin, phases, batch, faulty != nullptr, order != nullptr);
+    if (rc != BA_OK) return rc;
+    if (counters) memset(counters, 0, sizeof *counters);
+    if (batch == 0) return BA_OK;
+    HostRun r;
+    r.faulty = faulty, r.order = order, r.decisions = decisions, r.outcome = outcome, r.counters = counters;
+    r.extra = decided, r.extra_elem = 1, r.extra_behind_dec = false;
+    r.chunk_env = "BA_RSTALL_HOST_CHUNK";
+    r.queue = [=](const ba_params& q, uint64_t nt, const uint32_t* d_f, const uint8_t* d_o,
+                  uint64_t* d_dec, uint8_t* d_out, void* d_extra, uint64_t* d_cnt, hipStream_t st) {
+        return ba_rstall_run_trials_device(ctx, &q, coin, phases, nt, d_f, d_o, d_dec, d_out,
+                                           (uint8_t*)d_extra, d_cnt, st);
     };
     return host_run(ctx, p, batch, r);
 }

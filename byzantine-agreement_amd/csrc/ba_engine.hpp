@@ -234,6 +234,11 @@ constexpr uint32_t kRandMaxPhases = 64;
 hipError_t launch_rand(const RunArgs& a, uint32_t policy, uint32_t coin, uint32_t phases,
                        uint8_t* decided);
 
+// RAND against the stalling adversary (ba_rstall.hip, docs/SEMANTICS.md §15): RAND's
+// arguments without a policy; phases = R, 1..kRstallMaxPhases.  decided optional.
+constexpr uint32_t kRstallMaxPhases = 250;
+hipError_t launch_rstall(const RunArgs& a, uint32_t coin, uint32_t phases, uint8_t* decided);
+
 // Phase King and KING3 against every traitor strategy of one case (ba_kenum.hip,
 // docs/SEMANTICS.md §11): trial t is strategy S = t.  Everything the kernel needs
 // is in the case: no map, no upload.  n is a template parameter of k_kenum (the

@@ -1,10 +1,11 @@
 // ba_wave_proto.hpp -- what the word-per-wave protocol kernels share: k_sm
-// (ba_sm.hip), k_adv (ba_adv.hip), k_king (ba_king.hip), k_king3 (ba_king3.hip) and
-// k_rand (ba_rand.hip); k_enum (ba_enum.hip) and the host take general_mask.  Each holds
+// (ba_sm.hip), k_adv (ba_adv.hip), k_king (ba_king.hip), k_king3 (ba_king3.hip),
+// k_rand (ba_rand.hip) and k_rstall (ba_rstall.hip); k_enum (ba_enum.hip) and the host take general_mask.  Each holds
 // 64-trial words bit-sliced in wave-private LDS planes, takes the trials' inputs
 // with lane = trial, and ends a word with lane = trial again: a bit column picked
 // out of the planes, trial_result, and the word's counters folded into one lane
-// per counter.
+// per counter.  (k_rstall keeps lane = trial throughout and takes the prologue and the
+// epilogue only.)
 #pragma once
 #include "ba_engine.hpp"
 

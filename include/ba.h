@@ -505,6 +505,43 @@ int ba_rand_run_trials_device(struct ba_ctx* ctx, const ba_params* p, uint32_t p
  * 1..32, phases outside 1..64 or coin > 1. */
 uint64_t ba_rand_coin_calls(uint32_t n, uint32_t phases, uint32_t coin);  /* host only */
 
+/* ---- RAND against a stalling adversary that sees the loyal state ----------------
+ * RAND's rules, tosses, decided byte, epilogue and in-bound rule above, unchanged
+ * (docs/SEMANTICS.md §15; no ba.py analogue); only what a faulty sender shows differs,
+ * and no message coin is drawn.  With F the faulty set, f = |F| and rank(j) the number
+ * of faulty generals below j:
+ *   round 0      a faulty commander shows a loyal lieutenant r the bit r & 1 and a
+ *                faulty one retreat;
+ *   report       with a the number of loyal generals whose x is attack at the start of
+ *                the phase and t = min(max(floor(n/2) - a, 0), f), a faulty j shows
+ *                every loyal general attack iff rank(j) < t, and a faulty one retreat:
+ *                every loyal general counts c1 = a + t, as near floor(n/2) as can be;
+ *   propose      with P1 and P0 the loyal generals that propose attack and retreat, a
+ *                faulty j shows every loyal general retreat if P1 > P0, else attack,
+ *                and a faulty one no proposal.
+ * The adversary reads x after the previous phase's toss, which is all a synchronous
+ * adversary can see before it speaks; it does not rush the coin within a phase, and it
+ * is no worst case for safety.  In bound it keeps local coins undecided until all loyal
+ * tosses of a phase fall alike, and costs the common coin one phase.
+ * Arguments and errors are ba_rand_run_trials' without the policy: p->m <= 10,
+ * p->lie_mode BA_LIE_PHILOX (TABLE: BA_ENOTSUP), p->engine BA_ENGINE_AUTO, coin <=
+ * BA_RAND_COMMON, phases in 1..BA_RSTALL_MAX_PHASES (else BA_EINVAL). */
+#define BA_RSTALL_MAX_PHASES 250
+int ba_rstall_run_trials(struct ba_ctx* ctx, const ba_params* p, uint32_t coin, uint32_t phases,
+                         uint64_t batch, const uint32_t* faulty_mask, const uint8_t* order,
+                         uint64_t* decisions, uint8_t* outcome, uint8_t* decided,
+                         ba_counters* counters);   /* counters overwritten */
+/* The same phases on device buffers, enqueued on `stream` in the ctx's call order
+ * (NULL = HIP's null stream). */
+int ba_rstall_run_trials_device(struct ba_ctx* ctx, const ba_params* p, uint32_t coin,
+                                uint32_t phases, uint64_t batch, const uint32_t* d_faulty_mask,
+                                const uint8_t* d_order, uint64_t* d_decisions, uint8_t* d_outcome,
+                                uint8_t* d_decided, uint64_t* d_counters,
+                                void* stream);   /* accumulated, async */
+/* R (LOCAL ? n : 1): Philox calls per 64-trial word when every toss is drawn.  0 for n
+ * outside 1..32, phases outside 1..250 or coin > 1. */
+uint64_t ba_rstall_coin_calls(uint32_t n, uint32_t phases, uint32_t coin);  /* host only */
+
 /* ---- Phase King and KING3 against every traitor strategy of one case -----------
  * BA_KING_COIN and BA_KING_SPLIT are two adversaries; the theorems (agreement whenever
  * n > 4m, n > 3m) speak of every choice of messages.  These entries walk all of them
