@@ -6,6 +6,7 @@
 #pragma once
 #include "ba_bitslice.hpp"
 #include "ba_leaf.hpp"
+#include "ba_om3_task.hpp"
 
 namespace ba {
 
@@ -237,7 +238,7 @@ __device__ __forceinline__ void stage_words_sliced(uint64_t* in0, uint32_t lane,
     static_assert(W == 8, "lane = (word, byte): 8 words x 8 bytes");
     constexpr int NIN = N + 3;
     const StagePlanes<N> p = stage_pack<N>(stage_load(faulty, order, w0 * 64, 8 * lane, batch));
-    uint8_t* dst = reinterpret_cast<uint8_t*>(in0 + (lane >> 3) * NIN) + (lane & 7u);
+    uint8_t* dst = reinterpret_cast<uint8_t*>(in0) + mul_u24(lane >> 3, 8 * NIN) + (lane & 7u);
     static_for<0, NIN>([&](auto g) { dst[8 * g()] = (uint8_t)p.template plane<g()>(); });
 }
 
@@ -493,15 +494,18 @@ __device__ __forceinline__ void wave_epilogue(uint64_t* in0, const uint64_t* au0
 // wave_epilogue (lane = trial, one bfe + shift-or per output bit) is not run.
 // A lane whose live byte is not all ones stores trial by trial under the live
 // bit; nothing is stored at or beyond batch (the live plane is 0 there).
-template <int N, int W, uint32_t ME>
+// AUW: words of root planes per trial word in au0 (2L: A and U as wave_roots
+// and roots_r1t lay them out; L: the dense A image of Om3RootHalves, odd L).
+template <int N, int W, uint32_t ME, int AUW = 2 * (N - 1)>
 __device__ __forceinline__ void wave_epilogue_sliced(const uint64_t* in0, const uint64_t* au0,
                                                      uint32_t lane, uint64_t w0,
                                                      uint64_t* __restrict__ decisions,
                                                      uint8_t* __restrict__ outcome, TrialCounts& tc) {
     static_assert(W == 8, "lane = (word, byte): 8 words x 8 bytes");
     constexpr int L = N - 1, NIN = N + 3;
-    const uint8_t* ib = reinterpret_cast<const uint8_t*>(in0 + (lane >> 3) * NIN) + (lane & 7u);
-    const uint8_t* ab = reinterpret_cast<const uint8_t*>(au0 + (lane >> 3) * 2 * L) + (lane & 7u);
+    static_assert(AUW == 2 * L || (AUW == L && L % 2 == 1), "A and U planes, or A alone");
+    const uint8_t* ib = reinterpret_cast<const uint8_t*>(in0) + mul_u24(lane >> 3, 8 * NIN) + (lane & 7u);
+    const uint8_t* ab = reinterpret_cast<const uint8_t*>(au0) + mul_u24(lane >> 3, 8 * AUW) + (lane & 7u);
     uint32_t a[L], u[L], o[6];
     static_for<0, L>([&](auto b) {
         a[b()] = ab[8 * b()];
@@ -737,6 +741,13 @@ struct Om3LaneOffsets {
     __device__ __forceinline__ explicit Om3LaneOffsets(uint32_t la)
         : mem([la](int a) { return 8u * (a + ((uint32_t)a >= la ? 1u : 0u)); }),
           r2t([la](int d) { return (uint32_t)d >= la ? 8u * CP : 0u; }) {}
+    // the same two tables from their closed forms (om3_lane_tables, S <= 7)
+    __device__ __forceinline__ explicit Om3LaneOffsets(const Om3LaneTables& t)
+        : mem([](int) { return 0u; }), r2t([](int) { return 0u; }) {
+        static_assert(LaneBytes<S>::NB == 1, "one word per table");
+        mem.b[0] = t.mem;
+        r2t.b[0] = t.r2t;
+    }
     // a copy the compiler cannot see through, taken once per round
     __device__ __forceinline__ Om3LaneOffsets round_copy() const {
         Om3LaneOffsets o = *this;
@@ -1211,10 +1222,17 @@ __global__ __launch_bounds__(kWaveThreads, BA_OM3W_MIN_BLOCKS(N)) void k_om3wt(
         // lane-derived values per task, as in k_om3w
         uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
         asm volatile("" : "+v"(lane));
-        const uint32_t lw_ = lane / C, la = lane - lw_ * C;
+        // All 64 lanes hold a leaf block (W C = 64): the code around the rounds
+        // carries no `act` selects or exec masks.  om3_round keeps the run-time
+        // flag, whose branch is what separates its R1 step from the round block.
+        static_assert(G::LANES == 64 && C == 8 && L % 2 == 1, "k_om3wt: lane = (word, block) = (lane >> 3, lane & 7)");
+        // (lw opaque, as lane is: seen as lane >> 3, the table build's products become
+        // four running 64-bit sums across the rounds -- 6 more VGPRs, spills)
+        uint32_t lw = lane >> 3;
+        asm volatile("" : "+v"(lw));
+        const uint32_t la = lane & 7u;
         const bool act = lane < (uint32_t)G::LANES;
-        const uint32_t lw = act ? lw_ : 0;
-        const Om3LaneOffsets<N> lofs(la);
+        const Om3LaneOffsets<N> lofs(om3_lane_tables<G::S, G::CP>(la));
         const uint64_t w0 = task * W;
         const uint64_t gw0 = (first_trial >> 6) + w0;
         if constexpr (STAGED)
@@ -1223,34 +1241,39 @@ __global__ __launch_bounds__(kWaveThreads, BA_OM3W_MIN_BLOCKS(N)) void k_om3wt(
             wave_inputs<N, W, 0>(img + G::oIN, lane, w0, seed, gs, first_trial, batch, faulty, order);
         __builtin_amdgcn_wave_barrier();
         level0_r1t<N, W, G::LP>(img + G::oIN, img + G::oL0, img + G::oR1, lane, seed, gw0);
-        const uint64_t* in = img + G::oIN + lw * NIN;
-        uint64_t* erow = img + G::oE + lw * (C + 1);
-        if (act) erow[la] = in[la + 2];
+        // (lw < 8, la < 8: byte offsets by 24-bit multiplies)
+        const uint64_t* in = img + G::oIN + mul_u24(lw, NIN);
+        uint64_t* erow = img + G::oE + mul_u24(lw, C + 1);
+        erow[la] = in[la + 2];
         __builtin_amdgcn_wave_barrier();
         const uint64_t gw = gw0 + lw;
         // the lane's side of the pair table: its block's row, its builder step, and
         // the per-(word, level) constants of its own word at the leaf level
         Om3PairTable<N> tab;
-        tab.row = (char*)(img + G::oT) + la * (uint32_t)Om3PairTable<N>::ROW;
+        tab.row = (char*)(img + G::oT) + mul_u24(la, Om3PairTable<N>::ROW);
         tab.bw = lw < (uint32_t)Om3PairTable<N>::S ? lw : (uint32_t)Om3PairTable<N>::S - 1;
         tab.pair0 = 0;
         tab.gw_hi = (uint32_t)((first_trial >> 6) >> 32);
         tab.k1 = (uint32_t)(seed >> 32);
         tab.wc = philox_word_consts(ME, (uint32_t)gw, (uint32_t)seed, (uint32_t)(seed >> 32));
+        const uint64_t* l0w = lds_at(img + G::oL0, mul_u24(lw, 8 * L));
+        // R1[j1, b] is root input j1 of receiver column j2(b) = la + (la >= j1); the
+        // base is one product of L lw + la (split as 8 LP la + ..., the round's own
+        // R2T store shares 8 CP la with it and re-adds it inside the round block)
+        uint64_t* r1col = lds_at(img + G::oR1, mul_u24(mul_u24(lw, L) + la, 8 * G::LP));
         for (uint32_t j1 = 0; j1 < (uint32_t)L; ++j1) {
             wave_alternate_priority(j1);
-            const uint64_t r1 = om3_round<N, true>(in, act ? img[G::oL0 + lw * L + j1] : 0ull,
-                                                   img + G::oR2, lw, la, act, j1, seed, gw,
-                                                   erow, &lofs, (const Om3PairTable<N>*)&tab);
-            if (act) img[G::oR1 + (lw * L + la + (la >= j1 ? 1u : 0u)) * G::LP + j1] = r1;
+            const uint64_t r1 = om3_round<N, true>(in, l0w[j1], img + G::oR2, lw, la, act, j1, seed,
+                                                   gw, erow, &lofs, (const Om3PairTable<N>*)&tab);
+            r1col[(la >= j1 ? (uint32_t)G::LP : 0u) + j1] = r1;
         }
         __builtin_amdgcn_wave_barrier();
-        roots_r1t<L, W, G::LP>(img + G::oR1, img + G::oAU, lane);
+        Om3RootHalves<L, W, G::LP>::run(img + G::oR1, img + G::oAU, lane);
         __builtin_amdgcn_wave_barrier();
         {
             TrialCounts tc;
-            wave_epilogue_sliced<N, W, ME>(img + G::oIN, img + G::oAU, lane, w0, decisions, outcome,
-                                           tc);
+            wave_epilogue_sliced<N, W, ME, L>(img + G::oIN, img + G::oAU, lane, w0, decisions,
+                                              outcome, tc);
             wave_fold_packed<N, W>(tc, lane, img + G::oL0, folded);
         }
         __builtin_amdgcn_wave_barrier();
